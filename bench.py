@@ -6,9 +6,16 @@ U[400,600], V_w=2^20, Zipf s=1, seed 42).  One step = one full index build +
 TF-IDF weight pass over the HBM-resident corpus (sme_build_index_device): record
 split, docno lookup, tokenize/stop/stem, per-record tf aggregation, term sort,
 weights, and the reduce-order (tf desc, docno asc) postings.  The corpus is
-generated on the device before the timed region.  After the timed build steps,
-the c3 query batch (100k queries, 2-8 terms drawn by df, top-10) is timed the
-same way and reported in "query".
+generated on the device before the timed region.
+
+A plain run (`--gpus 1 --steps N --warmup W`) does only that: set-up, W warm-up
+steps, the N timed steps, the result line (`value`, `ms_per_step`, the stage
+times of the last step).  `--dump-outputs DIR` also writes the index of the last
+timed step as DIR/<name>.npy (dump_outputs), for output-for-output comparison of
+two builds of the library.  Everything below runs only with `--full`.
+
+--full: after the timed build steps, the c3 query batch (100k queries, 2-8 terms
+drawn by df, top-10) is timed the same way and reported in "query".
 
 --config c5: MS MARCO-shaped c5 (8,841,823 passages, V_w=30,000, 40-72 tokens,
 seed 9, strong scaling: the passages are split over the ranks) + 1M-query top-100;
@@ -78,6 +85,12 @@ def parse():
     p.add_argument("--docs", type=int, default=None, help="docs per GPU (weak) / in total (strong)")
     p.add_argument("--vocab", type=int, default=None)
     p.add_argument("--queries", type=int, default=None)
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step built to DIR/<name>.npy")
+    p.add_argument("--full", action="store_true",
+                   help="after the headline steps also run every other leg (records / query-ready / true-df builds, "
+                        "the query batch, HBM copy calibration, checks, end-to-end stage, CPU baselines); the "
+                        "options below only shape these legs")
     p.add_argument("--no-checks", action="store_true", help="skip the untimed post-run checks")
     p.add_argument("--cpu-docs", type=int, default=8000, help="docs in the ref-faithful CPU sample (0 = skip CPU)")
     p.add_argument("--cpu-opt-docs", type=int, default=50000, help="docs in the cpu-opt CPU sample")
@@ -89,6 +102,8 @@ def parse():
                    help="timed steps of the true-df leg (build + global df exchange + reweight; default --steps, "
                         "0 = skip)")
     a = p.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        p.error("--steps must be at least 1 and --warmup at least 0")
     cfg = dict(CONFIGS[a.config])
     for key in ("docs", "vocab", "queries"):
         if getattr(a, key) is not None:
@@ -245,33 +260,37 @@ def main():
     profs.append(ctx.last_build_profile())
     prof = {k: round(sum(p.get(k, 0.0) for p in profs) / len(profs), 4) for k in profs[-1]}
     N, V, P = ix.N, ix.V, ix.P
-    # the drop-in's product is the part files' records (TermKGramDocIndexer.java:
-    # 269-275): the same steps again with the I9 device serialization inside the
-    # clock (sme_index_serialize), reported as value_with_records beside value
-    barrier()
-    gc.disable()
-    t0 = time.perf_counter()
-    for _ in range(a.steps):
-        ix.close()
-        ix = step()
-        ix.serialize()
-    barrier()
-    dt_rec = (time.perf_counter() - t0) / a.steps
-    gc.enable()
-    # a drop-in that serves queries right after its build also pays the
-    # once-per-index query preparation (the reference's own post-build step is
-    # the forward-index job, BuildIntDocVectorsForwardIndex.java:84-158): the same
-    # steps with sme_index_prepare_queries inside the clock -> value_query_ready
-    barrier()
-    gc.disable()
-    t0 = time.perf_counter()
-    for _ in range(a.steps):
-        ix.close()
-        ix = step()
-        ix.prepare_queries(stream)
-    barrier()
-    dt_qr = (time.perf_counter() - t0) / a.steps
-    gc.enable()
+    if a.dump_outputs is not None and rank == 0:
+        dump_outputs(ix, a.dump_outputs)
+    dt_rec = dt_qr = 0.0
+    if a.full:
+        # the drop-in's product is the part files' records (TermKGramDocIndexer.java:
+        # 269-275): the same steps again with the I9 device serialization inside the
+        # clock (sme_index_serialize), reported as value_with_records beside value
+        barrier()
+        gc.disable()
+        t0 = time.perf_counter()
+        for _ in range(a.steps):
+            ix.close()
+            ix = step()
+            ix.serialize()
+        barrier()
+        dt_rec = (time.perf_counter() - t0) / a.steps
+        gc.enable()
+        # a drop-in that serves queries right after its build also pays the
+        # once-per-index query preparation (the reference's own post-build step is
+        # the forward-index job, BuildIntDocVectorsForwardIndex.java:84-158): the same
+        # steps with sme_index_prepare_queries inside the clock -> value_query_ready
+        barrier()
+        gc.disable()
+        t0 = time.perf_counter()
+        for _ in range(a.steps):
+            ix.close()
+            ix = step()
+            ix.prepare_queries(stream)
+        barrier()
+        dt_qr = (time.perf_counter() - t0) / a.steps
+        gc.enable()
     t_max = dt
     tot_bytes = nbytes
     if dist is not None:
@@ -296,7 +315,7 @@ def main():
 
     # ---- queries (c3) ----
     query = None
-    if not a.no_query and a.queries > 0:
+    if a.full and not a.no_query and a.queries > 0:
         query = run_queries(a, sme, synth, ix, torch, dist, world, rank, barrier)
 
     result = {
@@ -322,18 +341,6 @@ def main():
                      "what": "dominant kernel k_tok_fast: algorithmic bytes = text bytes B read once per launch, / "
                              "mean launch time (HIP events on its stream); traffic = PMC HBM bytes per launch "
                              "(profiles/pmc_traffic.json: 2 x FETCH_SIZE + WRITE_SIZE, gfx950 correction)"},
-        "value_with_records": {"value": round(tot_bytes / dt_rec / 1e9, 4), "unit": "GB/s",
-                               "ms_per_step": round(dt_rec * 1e3, 3),
-                               "what": "build + TF-IDF + I9 serialization of the partition records in HBM "
-                                       "(sme_index_serialize) per step, max over ranks; the records stay in HBM"
-                                       + ("" if world == 1 else "; per-shard records (the reference layout "
-                                          "needs dist.reference_partitions' exchange, not timed)")},
-        "value_query_ready": {"value": round(tot_bytes / dt_qr / 1e9, 4), "unit": "GB/s",
-                              "ms_per_step": round(dt_qr * 1e3, 3),
-                              "what": "build + TF-IDF + the once-per-index query preparation "
-                                      "(sme_index_prepare_queries: heavy tf / impact rows and their block "
-                                      "bounds, sparse posting words) per step, max over ranks: the index "
-                                      "ready to answer queries"},
         "build_roofline": {"achieved": round(achieved_build, 2), "unit": "GB/s",
                            "frac": round(achieved_build / HBM_PEAK_GBS, 5),
                            "what": "whole build step: A_build = B + 8P + 8(V+1) per GPU / step time"},
@@ -342,6 +349,32 @@ def main():
     if rehearse and world > 1:
         result["rehearsal"] = "SME_BENCH_REHEARSE: %d ranks on %d GPU(s), gloo -- not a scaling measurement" % (
             world, torch.cuda.device_count())
+
+    def finish():
+        if rank == 0:
+            print(json.dumps(result), flush=True)
+        L.sme_synth_free(d_corpus)
+        if dist is not None:
+            dist.destroy_process_group()
+
+    if not a.full:
+        # a plain run ends here: set-up, warm-up, the timed steps, the line
+        ix.close()
+        ctx.close()
+        finish()
+        return
+    result["value_with_records"] = {
+        "value": round(tot_bytes / dt_rec / 1e9, 4), "unit": "GB/s", "ms_per_step": round(dt_rec * 1e3, 3),
+        "what": "build + TF-IDF + I9 serialization of the partition records in HBM "
+                "(sme_index_serialize) per step, max over ranks; the records stay in HBM"
+                + ("" if world == 1 else "; per-shard records (the reference layout "
+                   "needs dist.reference_partitions' exchange, not timed)")}
+    result["value_query_ready"] = {
+        "value": round(tot_bytes / dt_qr / 1e9, 4), "unit": "GB/s", "ms_per_step": round(dt_qr * 1e3, 3),
+        "what": "build + TF-IDF + the once-per-index query preparation "
+                "(sme_index_prepare_queries: heavy tf / impact rows and their block "
+                "bounds, sparse posting words) per step, max over ranks: the index "
+                "ready to answer queries"}
     if query is not None:
         result["query"] = query
     # calibration: the achievable HBM rate of a streaming copy on this device,
@@ -382,11 +415,39 @@ def main():
             result["c1_sample"] = c1_sample(sme, a)
         if cpu_full is not None:
             result["cpu_baseline"]["cpu_opt"].update(cpu_full)
-    if rank == 0:
-        print(json.dumps(result), flush=True)
-    L.sme_synth_free(d_corpus)
-    if dist is not None:
-        dist.destroy_process_group()
+    finish()
+
+
+DUMP_SAMPLE = 1 << 20  # elements kept per dumped array (8 MiB as float64; six arrays: 48 MiB at most)
+DUMP_SEED = 20240229
+
+
+def dump_outputs(ix, out_dir):
+    """--dump-outputs: what a caller of the timed path holds after its last step,
+    the built index, as float64 .npy files.  stats = (N, V, P); the reduce-order
+    CSR of Index.csr() (offsets, docno, tf: tf desc / docno asc per term) and the
+    query-side arrays of Index.weights() (weight_docno: docno asc per term,
+    weight: the TF-IDF pass's fp64 output).  Arrays longer than DUMP_SAMPLE are
+    sampled at positions drawn once from DUMP_SEED and the array's length (the
+    same positions in every run of the same arguments), ascending; int32 / int64
+    values are exact in float64 (offsets stay far below 2^53)."""
+    os.makedirs(out_dir, exist_ok=True)
+
+    def put(name, arr):
+        if len(arr) > DUMP_SAMPLE:
+            pos = np.sort(np.random.default_rng([DUMP_SEED, len(arr)]).integers(0, len(arr), DUMP_SAMPLE))
+            arr = arr[pos]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float64))
+
+    put("stats", np.array([ix.N, ix.V, ix.P]))
+    off, dn, tf, _ = ix.csr()
+    put("offsets", off)
+    put("docno", dn)
+    put("tf", tf)
+    del off, dn, tf
+    _, wd, w = ix.weights()
+    put("weight_docno", wd)
+    put("weight", w)
 
 
 def true_df_leg(a, sme, ctx_args, mapping, d_corpus, nbytes, stream, D, barrier, world, torch, rehearse):

@@ -2,7 +2,7 @@
 set -o pipefail
 R=$GRAFT_REPO_ROOT; mkdir -p $R/gpurun_out/pmc
 cd /tmp && export TMPDIR=/tmp
-ARGS=${PMC_BENCH_ARGS:---docs 200000 --steps 1 --warmup 1 --no-query --cpu-docs 0}
+ARGS=${PMC_BENCH_ARGS:---full --docs 200000 --steps 1 --warmup 1 --no-query --cpu-docs 0}
 i=0
 for grp in "$@"; do
   i=$((i+1))
