@@ -188,6 +188,45 @@ int sme_chargram_partition_text(sme_index *ix, int part, const uint8_t **buf, si
 /* distinct k-grams (output lines) and (k-gram, token) set entries */
 int sme_chargram_stats(const sme_index *ix, uint64_t *ngrams, uint64_t *npairs);
 
+/* Open an index from its reduce-output record streams -- the step between the
+ * reference's two programs: TermKGramDocIndexer writes part-NNNNN SequenceFiles,
+ * IntDocVectorsForwardIndex opens them later (C/sa/edu/kaust/fwindex/
+ * BuildIntDocVectorsForwardIndex.java:84-158, IntDocVectorsForwardIndex.java:93-184).
+ * records = nparts partition streams laid back to back, part_offsets = nparts + 1
+ * host entries from 0, non-decreasing, the last one the byte count.  A stream
+ * is what sme_index_partition_records returns (int32 recLen, int32 keyLen,
+ * TermDF bytes, ArrayListWritable<PostingWritable> bytes; big-endian), and where
+ * a record would start, recLen == -1 followed by 16 bytes is a SequenceFile sync
+ * escape and is skipped: the bytes of a part file after its header load as they
+ * are (seqfile.read_part_body), with no per-record work on the host.
+ * nparts need not be cfg.num_partitions: the terms are merged into one TermDF
+ * order and the index serializes into cfg.num_partitions partitions.
+ * The result is the index sme_build_index returns for the corpus behind the
+ * records (vocabulary, both posting orders, fp64 weights, query side), with two
+ * differences: the " " doc counter never holds a map task's last docno
+ * (TermKGramDocIndexer.java:84-90,126), so the record is kept as its postings --
+ * serialization gives it back byte for byte -- and sme_index_record_docnos /
+ * sme_index_pack_pieces return SME_EINVAL.
+ * K = 1 only: cfg.k != 1, or a key whose component count is not 1, is
+ * SME_ENOTIMPL ("loading K >= 2 record streams"), decided before any per-term
+ * work.  Nothing in the input is trusted: every length is checked against its
+ * partition's end before a dependent read, and a malformed stream is SME_EPARSE
+ * with a message naming the first problem and its place (a record past its
+ * partition's end, keyLen or recLen inconsistent, a value class other than
+ * sa.edu.kaust.io.PostingWritable, key bytes writeUTF does not write, keys not
+ * strictly ascending in a partition or held by two, a stored df other than 1 /
+ * the " " posting count, no or several " " records, tf <= 0, postings out of
+ * (tf desc, docno asc) order, a docno twice in a term, " " postings other than
+ * (0,0) / (docno,1) lists); a term frequency >= 2^24 is SME_ELIMIT.
+ * sme_last_build_profile then holds the loader's stages (scan_candidates,
+ * scan_records, keys, merge_terms, postings, docno_order, weights, total).
+ * The host entry copies to HBM and calls the device entry (stream NULL =
+ * default stream; d_records on ctx's device). */
+int sme_index_from_records(sme_ctx *ctx, const uint8_t *records, const uint64_t *part_offsets, int nparts,
+                           sme_index **out);
+int sme_index_from_records_device(sme_ctx *ctx, const void *d_records, const uint64_t *part_offsets, int nparts,
+                                  void *stream, sme_index **out);
+
 void sme_index_free(sme_index *ix);
 
 /* N = records mapped (= df of the " " doc-counter key), V = distinct terms

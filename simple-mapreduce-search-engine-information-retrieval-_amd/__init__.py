@@ -51,7 +51,7 @@ EXPORTS = [
     "sme_split_points", "sme_split_points_device", "sme_index_term_fingerprints", "sme_set_option",
     "sme_index_prepare_queries", "sme_hbm_copy_bench", "sme_index_pack_pieces", "sme_merge_pieces",
     "sme_index_record_docnos", "sme_df_owner_pack", "sme_df_owner_sum", "sme_df_owner_unpack",
-    "sme_topk_merge_rows", "sme_count_shared_keys",
+    "sme_topk_merge_rows", "sme_count_shared_keys", "sme_index_from_records", "sme_index_from_records_device",
 ]
 
 
@@ -123,6 +123,8 @@ def lib():
     L.sme_df_owner_unpack.argtypes = [vp, vp, vp, C.c_int64, vp, vp]
     L.sme_topk_merge_rows.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_int, C.c_int, vp, vp, vp, vp]
     L.sme_count_shared_keys.argtypes = [vp, vp, C.c_int64, i64p, vp]
+    L.sme_index_from_records.argtypes = [vp, vp, C.POINTER(C.c_uint64), C.c_int, C.POINTER(vp)]
+    L.sme_index_from_records_device.argtypes = [vp, vp, C.POINTER(C.c_uint64), C.c_int, vp, C.POINTER(vp)]
     _lib = L
     return L
 
@@ -232,6 +234,32 @@ class Context:
         h = C.c_void_p()
         _check(lib().sme_build_index_device(self._h, C.c_void_p(d_ptr), nbytes, C.c_void_p(stream or 0),
                                             C.byref(h)))
+        return Index(h, self)
+
+    def load_records(self, parts):
+        """sme_index_from_records: an Index from its reduce-output record streams,
+        one bytes-like per partition (the bytes of a part-NNNNN file after its
+        SequenceFile header, sync escapes and all; seqfile.read_part_body).  The
+        partition count need not be this context's: terms are merged into one
+        order and the index serializes into num_partitions partitions."""
+        views = [np.frombuffer(b, dtype=np.uint8) for b in parts]
+        offs = (C.c_uint64 * (len(views) + 1))()
+        for i, v in enumerate(views):
+            offs[i + 1] = offs[i] + v.size
+        buf = np.concatenate(views) if views else np.zeros(0, np.uint8)
+        h = C.c_void_p()
+        _check(lib().sme_index_from_records(self._h, C.c_void_p(buf.ctypes.data if buf.size else 0), offs, len(views),
+                                            C.byref(h)))
+        return Index(h, self)
+
+    def load_records_device(self, d_ptr, part_offsets, stream=None):
+        """sme_index_from_records_device: the same from streams laid back to back
+        in HBM at d_ptr; part_offsets = len(parts) + 1 byte offsets from 0."""
+        n = len(part_offsets) - 1
+        offs = (C.c_uint64 * (n + 1))(*[int(x) for x in part_offsets])
+        h = C.c_void_p()
+        _check(lib().sme_index_from_records_device(self._h, C.c_void_p(d_ptr or 0), offs, n, C.c_void_p(stream or 0),
+                                                   C.byref(h)))
         return Index(h, self)
 
     def df_owner_pack(self, d_fp, d_df, n, world, d_send_fp, d_send_df, d_pos, stream=None):
@@ -604,6 +632,15 @@ class IntDocVectorsForwardIndex:
                 ids.append(_mutf8_decode(mapping[p + 2:p + 2 + ln]))
                 p += 2 + ln
             self._docids = ids
+
+    @classmethod
+    def from_dir(cls, ctx, index_dir, mapping=None):
+        """The reference's second program: open a reduce output directory
+        (part-00000 ...) written earlier -- by TermKGramDocIndexer.run here or by
+        the Hadoop job -- and answer queries from it (IntDocVectorsForwardIndex
+        ctor, IntDocVectorsForwardIndex.java:93-122)."""
+        from . import seqfile
+        return cls(seqfile.load_index_dir(ctx, index_dir), mapping)
 
     def getValue(self, terms):  # noqa: N802
         ids = self.index.lookup(list(terms))

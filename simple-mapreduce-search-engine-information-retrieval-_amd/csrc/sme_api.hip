@@ -44,6 +44,12 @@ void need_query_side(const sme_index *ix) {
     throw sme::Error(SME_EINVAL, "records-only index (merged shard pieces): query the shard indexes");
 }
 
+// an index loaded from record streams holds the doc counter's bytes, not every record's docno
+void need_record_docnos(const sme_index *ix) {
+  if (ix->from_records)
+    throw sme::Error(SME_EINVAL, "index loaded from records: the doc counter never holds a map task's last docno");
+}
+
 void set_device(sme_ctx *cx) { SME_HIP(hipSetDevice(cx->device)); }
 
 // DataInput.readUTF body -> UTF-16
@@ -503,6 +509,44 @@ int sme_build_index(sme_ctx *cx, const uint8_t *corpus, size_t nbytes, sme_index
   });
 }
 
+int sme_index_from_records_device(sme_ctx *cx, const void *d_records, const uint64_t *part_offsets, int nparts,
+                                  void *stream, sme_index **out) {
+  return guard([&] {
+    if (!cx || !out || nparts < 0 || (nparts > 0 && !part_offsets)) throw sme::Error(SME_EINVAL, "bad argument");
+    set_device(cx);
+    hipStream_t st = stream_of(cx, stream);
+    sme_index *ix = sme::load_records(cx, (const uint8_t *)d_records, part_offsets, nparts, st);
+    cx->last_profile = ix->profile;
+    *out = ix;
+  });
+}
+
+int sme_index_from_records(sme_ctx *cx, const uint8_t *records, const uint64_t *part_offsets, int nparts,
+                           sme_index **out) {
+  return guard([&] {
+    if (!cx || !out || nparts < 0 || (nparts > 0 && !part_offsets)) throw sme::Error(SME_EINVAL, "bad argument");
+    const size_t nbytes = nparts > 0 ? (size_t)part_offsets[nparts] : 0;
+    if (!records && nbytes) throw sme::Error(SME_EINVAL, "null argument");
+    set_device(cx);
+    hipStream_t st = cx->own_stream;
+    // the stream's device copy lives for this call only (a pooled block)
+    sme::DevBuf buf;
+    buf.pool = &cx->pool;
+    uint8_t *d = buf.as<uint8_t>(nbytes + 16);
+    if (nbytes) SME_HIP(hipMemcpyAsync(d, records, nbytes, hipMemcpyHostToDevice, st));
+    sme_index *ix = nullptr;
+    try {
+      ix = sme::load_records(cx, d, part_offsets, nparts, st);
+    } catch (...) {
+      (void)hipStreamSynchronize(st);  // kernels may still read the copy
+      throw;
+    }
+    SME_HIP(hipStreamSynchronize(st));
+    cx->last_profile = ix->profile;
+    *out = ix;
+  });
+}
+
 void sme_index_free(sme_index *ix) {
   if (!ix) return;
   sme_ctx *cx = ix->ctx;
@@ -808,6 +852,7 @@ int sme_index_record_docnos(sme_index *ix, const int32_t **d_docno, int64_t *n) 
   return guard([&] {
     if (!ix || !d_docno || !n) throw sme::Error(SME_EINVAL, "null argument");
     if (ix->job != 0) throw sme::Error(SME_EINVAL, "not a TermKGramDocIndexer index");
+    need_record_docnos(ix);
     *d_docno = (const int32_t *)ix->d_rec_docno.p;
     *n = ix->N;
   });
@@ -817,6 +862,7 @@ int sme_index_pack_pieces(sme_index *ix, int world, void *d_out, uint64_t *sizes
   return guard([&] {
     if (!ix || !sizes) throw sme::Error(SME_EINVAL, "null argument");
     need_query_side(ix);
+    need_record_docnos(ix);
     set_device(ix->ctx);
     hipStream_t st = stream_of(ix->ctx, stream);
     sme::pack_pieces(ix, world, (uint8_t *)d_out, sizes, st);

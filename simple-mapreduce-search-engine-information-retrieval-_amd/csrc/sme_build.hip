@@ -4792,7 +4792,15 @@ __global__ void k_reweight(const int64_t *off, int64_t V, const int32_t *tf, con
   }
 }
 
-void reweight_index(sme_index *ix, int64_t N, const int64_t *d_gdf, hipStream_t st) {
+// the same product per posting, for a caller that holds every posting's term id
+// (the record loader): no wave walks a million-posting list alone
+__global__ void k_reweight_flat(const uint32_t *term_of, const int32_t *tf, int64_t P, const double *lut,
+                                const double *idf, double *w) {
+  for (int64_t p = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; p < P; p += (int64_t)gridDim.x * blockDim.x)
+    w[p] = __dmul_rn(lut[tf[p]], idf[term_of[p]]);
+}
+
+void reweight_index(sme_index *ix, int64_t N, const int64_t *d_gdf, hipStream_t st, const uint32_t *d_term_of) {
   auto &W = ix->ctx->ws;
   std::vector<double> lut(ix->max_tf + 1, 0.0);
   for (int i = 1; i <= ix->max_tf; i++) lut[i] = 1.0 + log((double)i);
@@ -4811,7 +4819,11 @@ void reweight_index(sme_index *ix, int64_t N, const int64_t *d_gdf, hipStream_t 
     hipLaunchKernelGGL(k_term_idf, dim3((unsigned)std::min<int64_t>((ix->V + 255) / 256, 65536)), dim3(256), 0, st,
                        (const int64_t *)ix->d_off.p, ix->V, idf_ref, Nn, d_gdf, d_tab, sdf, d_tab + by_df.size(),
                        ix->idf_mode, (double *)ix->d_idf.p);
-  if (ix->V > 0)
+  if (ix->V > 0 && d_term_of && ix->P > 0)
+    hipLaunchKernelGGL(k_reweight_flat, dim3((unsigned)std::min<int64_t>((ix->P + 255) / 256, 65536)), dim3(256), 0, st,
+                       d_term_of, (const int32_t *)ix->d_tf_d.p, ix->P, d_lut, (const double *)ix->d_idf.p,
+                       (double *)ix->d_w.p);
+  else if (ix->V > 0)
     hipLaunchKernelGGL(k_reweight, dim3((unsigned)std::min<int64_t>((ix->V + 3) / 4, 65536)),
                        dim3(256), 0, st, (const int64_t *)ix->d_off.p, ix->V, (const int32_t *)ix->d_tf_d.p, d_lut,
                        idf_ref, d_gdf, Nn, d_tab, sdf, d_tab + by_df.size(), ix->idf_mode, (double *)ix->d_w.p);

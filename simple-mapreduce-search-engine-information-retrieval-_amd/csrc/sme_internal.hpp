@@ -106,6 +106,8 @@ struct sme_index {
   sme::DevBuf d_rec_docno;  // int32 [N]
   sme::DevBuf d_rec_first;  // u8 [N]: record starts a map task (split) -- merged shard pieces only
   bool records_only = false;  // merged shard pieces (sme_merge_pieces): reduce-order CSR + records, no query side
+  // loaded from record streams (sme_index_from_records): d_rec_docno lacks every map task's last docno
+  bool from_records = false;
   // serialized partitions (lazily built)
   sme::DevBuf d_ser;
   std::vector<int64_t> part_start;  // R+1
@@ -248,7 +250,13 @@ void serialize_index(sme_index *ix, hipStream_t st);
 // shard's terms and postings, and the owner's merge of the received blobs
 void pack_pieces(sme_index *ix, int world, uint8_t *d_out, uint64_t *sizes, hipStream_t st);
 sme_index *merge_pieces(sme_ctx *cx, const uint8_t *d_blobs, const uint64_t *sizes, int np, hipStream_t st);
-void reweight_index(sme_index *ix, int64_t N, const int64_t *d_gdf, hipStream_t st);
+// (d_term_of: the term id of every docno-order posting, if the caller has it --
+// the weights are then written by one flat pass over the postings)
+void reweight_index(sme_index *ix, int64_t N, const int64_t *d_gdf, hipStream_t st,
+                    const uint32_t *d_term_of = nullptr);
+// an index from np partition record streams laid back to back in device memory
+// (sme_load.hip; part_offsets: np + 1 host entries)
+sme_index *load_records(sme_ctx *cx, const uint8_t *d_records, const uint64_t *part_offsets, int np, hipStream_t st);
 void prepare_queries(sme_index *ix, hipStream_t st);
 // tie_bits: the reference tie word's tf width (24, or 22 when a query of the
 // batch has > 256 terms); 0 = decided by this batch.  Only the nested calls of

@@ -14,6 +14,9 @@ sme_index_partition_records).  This module is the host-side step after it:
                          every index record in TermDF.compareTo order ->
                          writeUTF(k_gram[0] + "\\t" + (fileNo * 1e9 + pos)), where pos is the
                          reader position before the record (header end for the first).
+  read_part_body /       SequenceFile.Reader.init [Hadoop 0.20]: the header checked field by
+  load_index_dir         field; what follows it (records and sync escapes) goes to the device
+                         loader as it is (sme_index_from_records).
   ForwardIndex           IntDocVectorsForwardIndex ctor + getValue(String)
                          (IntDocVectorsForwardIndex.java:93-122,148-184): term -> (file, pos)
                          -> one record read after seek.
@@ -91,6 +94,47 @@ def write_index_dir(ix, out_dir, sync=None):
         pos = write_sequence_file(os.path.join(out_dir, "part-%05d" % p), recs, sync)
         table[p] = [(key_of(recs, o), q) for (o, _), q in zip(iter_records(recs), pos)]
     return table
+
+
+def read_part_body(data):
+    """(body, sync) of one part file: the bytes after the SequenceFile header
+    (framed records, with an int32 -1 + sync escape before some of them) and the
+    file's 16-byte sync marker.  IOError unless the header is the one
+    SequenceFile.Writer writes for this job: version 6, TermDF keys,
+    ArrayListWritable values, no compression, no metadata."""
+    data = bytes(data) if not isinstance(data, (bytes, bytearray, memoryview)) else data
+    if bytes(data[:4]) != b"SEQ\x06":
+        raise IOError("not a SequenceFile v6")
+    p = 4
+    for what, want in (("key", KEY_CLASS), ("value", VALUE_CLASS)):
+        if p >= len(data):
+            raise IOError("truncated SequenceFile header")
+        ln = data[p]  # Text.writeString: vint length (< 128: one byte)
+        if ln >= 128 or bytes(data[p + 1:p + 1 + ln]) != want:
+            raise IOError("%s class is not %s" % (what, want.decode()))
+        p += 1 + ln
+    if len(data) < p + 2 + 4 + 16:
+        raise IOError("truncated SequenceFile header")
+    if data[p] != 0 or data[p + 1] != 0:
+        raise IOError("compressed SequenceFiles are not supported")
+    if struct.unpack_from(">i", data, p + 2)[0] != 0:
+        raise IOError("SequenceFile metadata is not empty")
+    p += 6
+    return data[p + 16:], bytes(data[p:p + 16])
+
+
+def load_index_dir(ctx, index_dir):
+    """Open a reduce output directory: part-00000, part-00001, ... up to the first
+    missing file, each file's body (sync escapes left in) as one partition of
+    Context.load_records.  Returns the Index."""
+    parts = []
+    while True:
+        path = os.path.join(index_dir, "part-%05d" % len(parts))
+        if not os.path.exists(path):
+            break
+        with open(path, "rb") as f:
+            parts.append(read_part_body(f.read())[0])
+    return ctx.load_records(parts)
 
 
 def key_grams(key):
