@@ -405,7 +405,19 @@ int sme_merge_pieces(sme_ctx *ctx, const void *d_blobs, const uint64_t *sizes, i
 
 /* Timing of the last build, per stage, in milliseconds (device events on the
  * build stream), as a JSON object; "tok_kernel" brackets exactly the tokenizer
- * launch and "query_kernel" (if a query batch ran) the last scoring launch. */
+ * launch and "query_kernel" (if a query batch ran) the last scoring launch.
+ * Beside the timings it carries integer path counters, so a caller (or a test)
+ * can tell which path ran:
+ *   tok_attempts, vocab_attempts, lt_attempts   passes of the build's capacity
+ *     loops (raw-vocabulary table, k_vocab's long-token / multi-term lists, the
+ *     '<' list): 1 each when the first capacity held;
+ *   query_overflow   k_query_win queries whose first candidate list overflowed,
+ *   query_fallback   of those, the queries finally scored by the block-max sweep,
+ *   query_split      1 when the batch was split by query range (table budget),
+ *   query_stages     k_query_win launches of the first round (1: not staged),
+ *   query_slices     query slices per window of those launches
+ * (the query_ counters only after a batch on the window kernel; of a split
+ * batch, stages and slices are those of its last part). */
 int sme_last_build_profile(const sme_ctx *ctx, const char **json);
 
 #ifdef __cplusplus

@@ -891,7 +891,8 @@ int sme_last_build_profile(const sme_ctx *cx, const char **json) {
     if (cx->last_query_ms >= 0) os << ",\"query_kernel_name\":\"" << cx->last_query_name << "\"";
     if (cx->last_query_ms >= 0 && cx->last_query_name == std::string("k_query_win"))
       os << ",\"query_seed\":" << cx->last_query_seed_ms << ",\"query_final\":" << cx->last_query_final_ms
-         << ",\"query_overflow\":" << cx->last_query_overflow << ",\"query_fallback\":" << cx->last_query_fallback << ",\"query_split\":" << (cx->last_query_split ? 1 : 0) << ",\"query_total\":" << cx->last_query_total_ms;
+         << ",\"query_overflow\":" << cx->last_query_overflow << ",\"query_fallback\":" << cx->last_query_fallback << ",\"query_stages\":" << cx->last_query_stages << ",\"query_slices\":" << cx->last_query_slices
+         << ",\"query_split\":" << (cx->last_query_split ? 1 : 0) << ",\"query_total\":" << cx->last_query_total_ms;
     os << "}";
     const_cast<sme_ctx *>(cx)->profile_json = os.str();
     *json = cx->profile_json.c_str();

@@ -2940,8 +2940,16 @@ __global__ void k_compact_flags(const uint8_t *flag, int64_t n, int64_t *list, u
 }
 __global__ void k_long_lens(const int64_t *list, int64_t n, const int32_t *rlist, const unsigned long long *rep,
                             int64_t *lens) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-    lens[i] = 5 * (int64_t)(rep[rlist[list[i]]] & 0xFFFFFFull) + 32;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    // The masked length goes through an empty asm: hipcc 7.2 (clang 22) compiled
+    // 5 * (rep & 0xFFFFFF) + 32 to one v_mad_u64_u32 on the unmasked low word (the
+    // 24-bit multiply-add it was formed from ignores the high byte, this one does
+    // not), so every length carried 5 * 2^24 * (token offset & 255) more units and
+    // a few thousand long tokens asked for terabytes of scratch.
+    uint32_t len = (uint32_t)(rep[rlist[list[i]]] & 0xFFFFFFull);
+    asm volatile("" : "+v"(len));
+    lens[i] = 5 * (int64_t)len + 32;
+  }
 }
 __global__ void k_big_list(const int32_t *prec, int64_t n, int64_t *list, unsigned long long *cnt) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
@@ -3596,7 +3604,9 @@ RecordSpans find_records(sme_ctx *cx, const uint8_t *t, uint64_t n, hipStream_t 
   uint64_t capL = std::max<uint64_t>(cx->lt_cap_hint, std::max<uint64_t>(4096, n / 256));
   uint64_t *ltpos = nullptr;
   int64_t nlt = 0;
+  int lt_attempts = 0;
   for (int attempt = 0;; attempt++) {
+    lt_attempts++;
     ltpos = W[W_LT].as<uint64_t>(capL);
     SME_HIP(hipMemsetAsync(cnt, 0, 16 * sizeof(unsigned long long), st));
     hipLaunchKernelGGL(k_scan_lt, dim3(grid_for((int64_t)ceil_div(n, 64), 256, 4096)), dim3(kScanNT), 0, st, t,
@@ -3673,7 +3683,7 @@ RecordSpans find_records(sme_ctx *cx, const uint8_t *t, uint64_t n, hipStream_t 
     }
   }
   if (prof) prof->mark("records");
-  return RecordSpans{rs, re, nR, C, nC};
+  return RecordSpans{rs, re, nR, C, nC, lt_attempts};
 }
 
 __global__ void k_iota_docno(int32_t *d, int64_t n) {
@@ -3781,8 +3791,12 @@ sme_index *build_index(sme_ctx *cx, const uint8_t *t, uint64_t n, hipStream_t st
   RawTable tb;
   unsigned int *ovf = reinterpret_cast<unsigned int *>(cnt + 8);
   int64_t h_nsel = 0;  // distinct raw tokens (read with the overflow flags)
+  // passes of the three capacity loops, reported in the profile ("tok_attempts",
+  // "vocab_attempts", "lt_attempts"): 1 each when nothing overflowed
+  int tok_attempts = 0, vocab_attempts = 0;
 
   for (int attempt = 0;; attempt++) {
+    tok_attempts++;
     {
       uint8_t *rb = W[W_RKEYS].as<uint8_t>(rcap * kRawSlotBytes);
       tb.tok = reinterpret_cast<ulonglong2 *>(rb);
@@ -3936,6 +3950,7 @@ vocab_again:  // (a docid term equal to a word term: the general path, from here
   uint64_t ovf_cap = std::max<uint64_t>(cx->vocab_ovf_cap, 4096);
   int64_t novf = 0, nlong = 0;
   for (int attempt = 0;; attempt++) {
+    vocab_attempts = std::max(vocab_attempts, attempt + 1);  // (the most of any pass through vocab_again)
     co.cand_str = W[W_CSTR].as<uint64_t>(nraw + ovf_cap);
     co.ovf_key = W[W_OVFKEY].as<uint64_t>(ovf_cap);
     co.ovf_cap = ovf_cap;
@@ -4187,6 +4202,9 @@ vocab_again:  // (a docid term equal to a word term: the general path, from here
     ix->V = V;
     ix->Vt = V;
     ix->profile = prof.finish();
+    ix->profile.emplace_back("tok_attempts", (float)tok_attempts);
+    ix->profile.emplace_back("vocab_attempts", (float)vocab_attempts);
+    ix->profile.emplace_back("lt_attempts", (float)rsp.lt_attempts);
     ix_guard.release();
     return ix;
   }
@@ -4770,6 +4788,9 @@ vocab_again:  // (a docid term equal to a word term: the general path, from here
   ix->V = Vi;
   ix->Vt = V;
   ix->profile = prof.finish();
+  ix->profile.emplace_back("tok_attempts", (float)tok_attempts);
+  ix->profile.emplace_back("vocab_attempts", (float)vocab_attempts);
+  ix->profile.emplace_back("lt_attempts", (float)rsp.lt_attempts);
   ix_guard.release();
   return ix;
 }

@@ -55,6 +55,13 @@ struct BufPool {
   }
 };
 
+// The build stage last marked on this thread (Prof::mark): names the place of an
+// allocation failure.
+inline const char *&last_stage() {
+  static thread_local const char *s = "";
+  return s;
+}
+
 // A device buffer that grows on demand and is kept across builds, so the
 // timed path does no hipMalloc once warmed up.  With a pool, blocks come from
 // and go back to it instead of hipMalloc/hipFree.
@@ -73,11 +80,19 @@ struct DevBuf {
           SME_HIP(hipFree(p));
       }
       p = nullptr;
+      cap = 0;  // (a failed allocation below leaves the buffer empty, not a null block of the old size)
       size_t nc = 0;
       if (pool) p = pool->take(bytes, &nc);
       if (!p) {
         nc = bytes + bytes / 8;
-        SME_HIP(hipMalloc(&p, nc));
+        const hipError_t e = hipMalloc(&p, nc);
+        if (e == hipErrorOutOfMemory) {
+          (void)hipGetLastError();
+          p = nullptr;
+          throw Error(SME_ENOMEM, "out of device memory allocating " + std::to_string(nc) + " bytes (after stage \"" +
+                                      last_stage() + "\")");
+        }
+        SME_HIP(e);
       }
       cap = nc;
     }

@@ -43,6 +43,8 @@ struct sme_ctx {
   float last_query_seed_ms = 0.0f, last_query_final_ms = 0.0f, last_query_total_ms = 0.0f;
   int64_t last_query_overflow = 0;  // k_query_win queries whose first candidate list overflowed
   int64_t last_query_fallback = 0;  // of those, queries finally scored by k_query_bm
+  int64_t last_query_stages = 0;    // k_query_win launches of the first round (1: unstaged)
+  int64_t last_query_slices = 0;    // query slices per window of that round's launches
   bool last_query_split = false;     // the batch was split by query range (table budget)
   // Path options (sme_set_option).  Every setting gives identical results; they
   // exist so tests can hold each path to the others and benches can sweep them.
@@ -174,6 +176,7 @@ struct Prof {
       SME_HIP(hipEventCreate(&e));
     }
     ev.emplace_back(name, e);
+    last_stage() = name;
     SME_HIP(hipEventRecord(e, st));
   }
   std::vector<std::pair<std::string, float>> finish() {
@@ -198,6 +201,7 @@ struct RecordSpans {
   int64_t nR;
   uint64_t *C;        // sorted positions of '<' whose markup is not "simple"
   int64_t nC;
+  int lt_attempts;   // passes of the '<' list loop (1: the first capacity held)
 };
 void build_docid_hash(sme_ctx *cx, bool distinct, hipStream_t st);
 RecordSpans find_records(sme_ctx *cx, const uint8_t *d_text, uint64_t n, hipStream_t st, Prof *prof);

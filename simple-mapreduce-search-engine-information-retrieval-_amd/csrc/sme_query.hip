@@ -2701,6 +2701,7 @@ void query_topk(sme_index *ix, const int32_t *d_terms, const int64_t *d_qoff, in
   };
   const bool win = tiled && cx->opt_query_kernel == 0 && ix->q_spk;
   int64_t n_ovf = 0;
+  int64_t n_stages = 0, n_slices = 0;  // round 0 of k_query_win: launches, query slices per launch
   bool subset_ran = false;  // the overflow fallback answered queries as nested compact batches
   QTimes sub_times;
   if (win) {
@@ -2848,6 +2849,7 @@ void query_topk(sme_index *ix, const int32_t *d_terms, const int64_t *d_qoff, in
         hipLaunchKernelGGL(k_query_win, dim3((unsigned)wg), dim3(kWNT), dyn_lds, st, wa);
       }
       SME_CHECK_LAUNCH();
+      if (round_list == nullptr) n_stages++;  // (round 0)
     };
     for (int round = 0; round < kWinRounds && n_round > 0; round++) {
       if (round > 0) {
@@ -2862,6 +2864,7 @@ void query_topk(sme_index *ix, const int32_t *d_terms, const int64_t *d_qoff, in
       // the launch is large anyway and c5 does not gain)
       const int64_t qps = cx->opt_win_slice > 0 ? cx->opt_win_slice : (nwin >= 1024 ? 256 : 128);
       wa.nslices = (int)std::max<int64_t>(1, std::min<int64_t>(n_round / qps, 4096));
+      if (round == 0) n_slices = wa.nslices;
       if (round == 0 && cx->opt_win_sample && nwin >= 16) {
         for (int sg = 0; sg <= L; sg++) {
           if (sg > 0) {  // raise thresholds, keep each list's best k
@@ -2997,6 +3000,8 @@ void query_topk(sme_index *ix, const int32_t *d_terms, const int64_t *d_qoff, in
   cx->last_query_final_ms = fms;
   cx->last_query_total_ms = sms + ms + fms;
   cx->last_query_overflow = n_ovf;
+  cx->last_query_stages = n_stages;
+  cx->last_query_slices = n_slices;
   cx->last_query_index_ms = tiled ? ix->q_prep_ms : 0.0f;
   cx->last_query_tiled = tiled;
   cx->last_query_name = win ? "k_query_win" : tiled ? "k_query_bm" : "k_query";

@@ -96,6 +96,31 @@ def fuzz_corpus(seed, n_docs, hard=True, extra_docids=0, with_quirks=True):
     return body.encode("utf-8"), mapping
 
 
+def check_index(ix, ref, R, K=1):
+    """A device index (any context, fresh or reused) against the oracle's index of
+    the same corpus and mapping: N, every partition's records bit for bit, and
+    for K = 1 the reduce-order CSR view (vocabulary, V, P, every posting).  The
+    oracle's term list is computed once per `ref` and kept on it."""
+    assert ix.N == ref.N
+    for p in range(R):
+        compare_partitions(ix.partition_records(p), ref.partition_bytes(p))
+    if K > 1:
+        return
+    # CSR view equals the oracle's reduce output
+    off, dn, tf, df = ix.csr()
+    rterms = getattr(ref, "_rterms", None)
+    if rterms is None:
+        rterms = sorted([t for t in ref.terms() if t[0] != (" ",)],
+                        key=lambda t: t[0][0].encode("utf-16-be", "surrogatepass"))
+        ref._rterms = rterms
+    assert ix.V == len(rterms)
+    assert ix.P == sum(len(t[3]) for t in rterms)
+    for i, t in enumerate(rterms):
+        assert ix.term(i) == t[0][0]
+        got = list(zip(dn[off[i]:off[i + 1]].tolist(), tf[off[i]:off[i + 1]].tolist()))
+        assert got == [tuple(p) for p in t[3]]
+
+
 def canon_digest(buf):
     """sha256 of a partition's record stream with the " " doc-counter record's
     postings sorted (their order is Hadoop-defined): equal digests

@@ -45,3 +45,66 @@ def test_df_owner_steps(sme, n, world, collide):
     got = dev.unpack(ret.cuda(), torch.from_numpy(pos).cuda()).cpu().numpy()
     assert np.array_equal(got, ret.numpy()[pos])
     ctx.close()
+
+
+def _shared_rows(n, world, g):
+    """(key, source rank) rows as dist.merge_topk_owner builds them: keys are
+    docnos zero-extended from 32 bits (negative docnos become 0xFFFFFFFD and the
+    like, never the table's 64-bit empty marker).  A third of the keys arrive
+    from one rank only (some of them several times from that rank: not shared),
+    the others from 2, 3 or all `world` ranks, rows shuffled."""
+    if n == 0:
+        return np.zeros((0, 2), np.int64)
+    nk = max(n // 3, 1)
+    docno = np.unique(np.concatenate([g.integers(-50, 1 << 31, size=nk), np.array([-1, -3, -2147483648, 0, 2147483647])]))
+    keys = (docno.astype(np.int64) & 0xFFFFFFFF)[g.permutation(len(docno))]
+    rows = []
+    for i, key in enumerate(keys.tolist()):
+        kind = i % 6
+        if kind < 2:  # one rank only, kind 1 repeated inside that rank
+            r = int(g.integers(0, world))
+            rows += [(key, r)] * (1 + 3 * kind)
+        else:
+            m = min(world, (2, 3, world, 2)[kind - 2])
+            for r in g.permutation(world)[:m].tolist():
+                rows += [(key, r)] * (1 + (kind == 5))  # kind 5: each of two ranks sends it twice
+        if len(rows) >= n:
+            break
+    rows = np.array(rows[:n], np.int64).reshape(-1, 2)
+    return rows[g.permutation(len(rows))]
+
+
+@pytest.mark.parametrize("n,world", [(0, 2), (1, 1), (1000, 4), (70000, 5)])
+def test_count_shared_keys_device(sme, n, world):
+    """sme_count_shared_keys (k_shared_insert: a device hash of key -> first
+    source, sized 2n slots with a floor of 1024) against its numpy restatement:
+    distinct keys that arrive from two or more ranks."""
+    D = importlib.import_module(PKG + ".dist")
+    rows = _shared_rows(n, world, np.random.default_rng(7 * n + world))
+    assert rows.shape[0] == n
+    ctx = sme.Context()
+    dev, host = D.DeviceDfOps(ctx), HostDfOps()
+    expect = host.count_shared(torch.from_numpy(rows))
+    if n >= 1000:
+        assert 0 < expect < len(np.unique(rows[:, 0]))  # shared and unshared keys both present
+        assert (rows[:, 0] > 0xFFFFFF00).any()  # zero-extended negative docnos
+    assert dev.count_shared(torch.from_numpy(rows)) == expect
+    # the context's table is reused: a second, smaller call sees no stale slots
+    small = rows[:300]
+    assert dev.count_shared(torch.from_numpy(small)) == host.count_shared(torch.from_numpy(small))
+    ctx.close()
+
+
+@pytest.mark.parametrize("world,expect", [(1, 0), (8, 1)])
+def test_count_shared_keys_one_key(sme, world, expect):
+    """Every row holds the same key: one slot, every thread's compare-and-swap on
+    it.  From one rank it is not shared; from 8 ranks it counts once."""
+    D = importlib.import_module(PKG + ".dist")
+    n = 70000
+    rows = np.empty((n, 2), np.int64)
+    rows[:, 0] = 0xFFFFFFFD
+    rows[:, 1] = np.arange(n) % world
+    ctx = sme.Context()
+    assert HostDfOps().count_shared(torch.from_numpy(rows)) == expect
+    assert D.DeviceDfOps(ctx).count_shared(torch.from_numpy(rows)) == expect
+    ctx.close()

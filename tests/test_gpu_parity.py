@@ -44,20 +44,7 @@ def _check_build(sme, corpus, mapping_ids, R=1, idf_mode=0, K=1, tiebreak=0, opt
         ctx.set_option(name, v)
     ctx.load_docno_mapping(mb)
     ix = ctx.build(corpus)
-    assert ix.N == ref.N
-    for p in range(R):
-        common.compare_partitions(ix.partition_records(p), ref.partition_bytes(p))
-    if K > 1:
-        return ix, ref
-    # CSR view equals the oracle's reduce output
-    off, dn, tf, df = ix.csr()
-    rterms = sorted([t for t in ref.terms() if t[0] != (" ",)], key=lambda t: t[0][0].encode("utf-16-be", "surrogatepass"))
-    assert ix.V == len(rterms)
-    assert ix.P == sum(len(t[3]) for t in rterms)
-    for i, t in enumerate(rterms):
-        assert ix.term(i) == t[0][0]
-        got = list(zip(dn[off[i]:off[i + 1]].tolist(), tf[off[i]:off[i + 1]].tolist()))
-        assert got == [tuple(p) for p in t[3]]
+    common.check_index(ix, ref, R, K)  # N, partition records, CSR view (K = 1)
     return ix, ref
 
 
@@ -233,6 +220,13 @@ def _query_opts(ix, terms, qoff, k, **opts):
             ix.ctx.set_option(n, defaults[n])
 
 
+QUERY_VARIANTS = [{"heavy_div": 0}, {"heavy_div": 1 << 30}, {"heavy_div": 1}, {"seed_m": 0}, {"cand_cap": 4},
+                  {"win_sample": 0}, {"cand_cap": 16, "seed_m": 0},
+                  {"cand_cap": 1, "heavy_div": 1}, {"query_kernel": 2}, {"query_kernel": 2, "seed_tiles": 0},
+                  {"query_kernel": 2, "seed_tiles": 8, "query_order": 0}, {"query_kernel": 2, "heavy_div": 0},
+                  {"query_kernel": 1}]
+
+
 def _query_both_kernels(ix, terms, qoff, k):
     """Default window-major scoring (seeded threshold, heavy impact rows for terms
     covering >= 1/32 of the docno span), the same on postings only, every term
@@ -242,12 +236,7 @@ def _query_both_kernels(ix, terms, qoff, k):
     (register lists for k <= 32, the LDS candidate list above): all identical bits."""
     dn, sc = ix.query_topk(terms, qoff, k)
     assert ix.ctx.last_build_profile()["query_kernel_name"] in ("k_query_win", "k_query")
-    variants = [{"heavy_div": 0}, {"heavy_div": 1 << 30}, {"heavy_div": 1}, {"seed_m": 0}, {"cand_cap": 4},
-                {"win_sample": 0}, {"cand_cap": 16, "seed_m": 0},
-                {"cand_cap": 1, "heavy_div": 1}, {"query_kernel": 2}, {"query_kernel": 2, "seed_tiles": 0},
-                {"query_kernel": 2, "seed_tiles": 8, "query_order": 0}, {"query_kernel": 2, "heavy_div": 0}]
-    variants.append({"query_kernel": 1})
-    for v in variants:
+    for v in QUERY_VARIANTS:
         dn2, sc2 = _query_opts(ix, terms, qoff, k, **v)
         assert np.array_equal(dn, dn2) and np.array_equal(sc, sc2), v
     return dn, sc
