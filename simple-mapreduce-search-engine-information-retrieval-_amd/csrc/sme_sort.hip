@@ -677,8 +677,11 @@ void rs_scan(uint32_t *gsum, int64_t n, uint32_t *sums, hipStream_t st) {
 
 // Stable sort of P (key, packed value) pairs by the low `bits` bits of key.
 // k0/v0 hold the input; k1/v1 are a second buffer pair of the same size.  The
-// sorted keys end in k0 or k1 (returned); the values are unpacked into docno /
-// tf.  counts: ceil(P / 16384) * 2048 + 2048 * 256 u32 of scratch.
+// sorted keys end in k0 or k1 (returned: k1 after an odd number of passes, k0
+// after an even one or when P == 0); the values are unpacked into docno / tf.
+// counts: term_sort_scratch(P) bytes of scratch = ceil(P / 8192) * 2048 tile
+// counts + 2048 * 1024 (digit, group) sums + 1024 scan sums, all u32, then
+// ceil(P / 1024) + 1 int64 (gather mode's chunk table).
 uint32_t *term_sort(uint32_t *k0, uint32_t *v0, uint32_t *k1, uint32_t *v1, int64_t nrec, const int64_t *reg,
                     const int64_t *xoff, int64_t P, int bits, int64_t dmin, uint32_t F, int32_t *docno, int32_t *tf,
                     uint32_t *counts, hipStream_t st, const double *lut, double idf, double *w, int maxbits,
@@ -739,7 +742,8 @@ size_t term_sort_scratch(int64_t P) {
 }
 // Stable sort of n (key, u32 value) pairs by the low `bits` bits of the key
 // (11-bit digits).  k0/v0 hold the input, k1/v1 are second buffers of the same
-// size; returns the buffer holding the sorted values (v0 or v1).  The sorted
+// size; returns the buffer holding the sorted values (v1 after an odd number of
+// passes, v0 after an even one or when n <= 1).  The sorted
 // keys are in the matching key buffer (k0 or k1) when keys_out, else the last
 // pass does not write them.  scratch: kv_sort_scratch(n) bytes.
 template <typename K>
