@@ -137,6 +137,9 @@ void sme_destroy(sme_ctx *ctx);
  *                   many bytes (default 16 GiB); larger copies are freed after
  *                   the build, since HBM held there also shrinks the heavy-row
  *                   budget of sme_index_prepare_queries (1/4 of free HBM)
+ *   "wild_scan"     wildcard expansion: 0 (default) candidates from the trigram table, 1 every
+ *                   pattern takes the whole vocabulary as candidates
+ *   "wild_chunk"    wildcard candidates per workgroup, 64..4096 in multiples of 64 (default 1024)
  * Unknown names and out-of-range values are SME_EINVAL. */
 int sme_set_option(sme_ctx *ctx, const char *name, int64_t value);
 
@@ -281,6 +284,40 @@ int sme_tokenize(sme_ctx *ctx, const uint8_t *utf8, size_t n, uint8_t *buf, size
  * keeps it (IntDocVectorsForwardIndex.java:107-120). */
 int sme_lookup_terms(sme_index *ix, const uint8_t *terms, const int64_t *offs, int n,
                      int32_t *term_ids);
+
+/* Wildcard term expansion (no reference counterpart: the reference's character
+ * k-gram job, CharKGramTermIndexer, writes its gram -> term sets to text and no
+ * program reads them).  A pattern is matched against whole term strings, UTF-16
+ * unit by unit as String.compareTo sees them: '*' matches any run of units,
+ * none included; '?' exactly one unit (a supplementary character needs "??");
+ * every other unit itself.  No escape syntax and no case folding.  patterns /
+ * offs delimit n UTF-8 patterns on the host as sme_lookup_terms takes terms;
+ * malformed UTF-8 is SME_EINVAL (the message names the pattern's index), a
+ * pattern of more than 255 units SME_ELIMIT.  Pattern i's matches are
+ * term_ids[match_off[i] .. match_off[i + 1]), ascending (TermDF order); n + 1
+ * offsets, ids back to back, owned by the index until the next expansion on it
+ * (host memory from the host entry; device memory from the device entry, ready
+ * to be spliced into a sme_query_topk_device batch, with *total = match_off[n],
+ * total may be NULL).  n == 0 is valid; 2^31 or more matches in a batch are
+ * SME_ELIMIT.  Candidates come from a character-trigram table of the vocabulary
+ * (windows of three over START + units + END; a pattern's windows lie inside its
+ * literal runs) and every candidate is verified against the term's own units, so
+ * a pattern without a trigram ("*a*", "?b", "*", "") scans the vocabulary.  The
+ * table is built once per index, on first use or by sme_index_prepare_wildcards
+ * (*ms, may be NULL: its device time); it depends on the vocabulary only, so
+ * sme_index_reweight leaves it alone, and its HBM (8 B per distinct trigram, 4 B
+ * per (trigram, term) pair) stays held until the index is freed, so it counts
+ * against the heavy-row budget of sme_index_prepare_queries.
+ * sme_index_wildcard_stats (builds the table if needed): distinct trigram keys
+ * and distinct (key, term) pairs.  K = 1 term indexes only: a chargram output, a
+ * records-only merged index or K != 1 is SME_EINVAL (the message says which). */
+int sme_index_prepare_wildcards(sme_index *ix, void *stream, float *ms);
+int sme_index_wildcard_stats(sme_index *ix, uint64_t *ngrams, uint64_t *npairs);
+int sme_index_expand_wildcards(sme_index *ix, const uint8_t *patterns, const int64_t *offs, int n,
+                               const int64_t **match_off, const int32_t **term_ids);
+int sme_index_expand_wildcards_device(sme_index *ix, const uint8_t *patterns, const int64_t *offs, int n,
+                                      void *stream, const int64_t **d_match_off, const int32_t **d_term_ids,
+                                      int64_t *total);
 
 /* Batched rank(): query q has term ids term_ids[q_offsets[q] .. q_offsets[q+1])
  * in query-token order (duplicates count twice, -1 entries are skipped; an id

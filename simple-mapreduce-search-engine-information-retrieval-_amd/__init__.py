@@ -52,6 +52,8 @@ EXPORTS = [
     "sme_index_prepare_queries", "sme_hbm_copy_bench", "sme_index_pack_pieces", "sme_merge_pieces",
     "sme_index_record_docnos", "sme_df_owner_pack", "sme_df_owner_sum", "sme_df_owner_unpack",
     "sme_topk_merge_rows", "sme_count_shared_keys", "sme_index_from_records", "sme_index_from_records_device",
+    "sme_index_prepare_wildcards", "sme_index_wildcard_stats", "sme_index_expand_wildcards",
+    "sme_index_expand_wildcards_device",
 ]
 
 
@@ -125,6 +127,11 @@ def lib():
     L.sme_count_shared_keys.argtypes = [vp, vp, C.c_int64, i64p, vp]
     L.sme_index_from_records.argtypes = [vp, vp, C.POINTER(C.c_uint64), C.c_int, C.POINTER(vp)]
     L.sme_index_from_records_device.argtypes = [vp, vp, C.POINTER(C.c_uint64), C.c_int, vp, C.POINTER(vp)]
+    L.sme_index_prepare_wildcards.argtypes = [vp, vp, C.POINTER(C.c_float)]
+    L.sme_index_wildcard_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.sme_index_expand_wildcards.argtypes = [vp, C.c_char_p, i64p, C.c_int, C.POINTER(i64p), C.POINTER(i32p)]
+    L.sme_index_expand_wildcards_device.argtypes = [vp, C.c_char_p, i64p, C.c_int, vp, C.POINTER(vp), C.POINTER(vp),
+                                                    i64p]
     _lib = L
     return L
 
@@ -482,6 +489,52 @@ class Index:
         _check(lib().sme_index_prepare_queries(self._h, C.c_void_p(stream or 0), C.byref(ms)))
         return ms.value
 
+    def prepare_wildcards(self, stream=None):
+        """Build the vocabulary's character-trigram table now (else the first
+        expansion does); returns its device build time in ms."""
+        ms = C.c_float(0.0)
+        _check(lib().sme_index_prepare_wildcards(self._h, C.c_void_p(stream or 0), C.byref(ms)))
+        return ms.value
+
+    def wildcard_stats(self):
+        """(distinct trigram keys, distinct (key, term) pairs) of the wildcard table."""
+        a, b = C.c_uint64(), C.c_uint64()
+        _check(lib().sme_index_wildcard_stats(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    @staticmethod
+    def _pattern_args(patterns):
+        bs = [p if isinstance(p, (bytes, bytearray)) else p.encode("utf-8", "surrogatepass") for p in patterns]
+        offs = np.zeros(len(bs) + 1, dtype=np.int64)
+        if bs:
+            offs[1:] = np.cumsum([len(b) for b in bs])
+        return b"".join(bs), offs, len(bs)
+
+    def expand_wildcards(self, patterns):
+        """sme_index_expand_wildcards: patterns (str, or bytes of UTF-8) -> (match_off
+        int64[n+1], term_ids int32); pattern i matches term_ids[match_off[i]:
+        match_off[i+1]], ascending.  '*' = any run of UTF-16 units, '?' = one unit;
+        no case folding (include/sme.h)."""
+        blob, offs, n = Index._pattern_args(patterns)
+        mo, ti = C.POINTER(C.c_int64)(), C.POINTER(C.c_int32)()
+        _check(lib().sme_index_expand_wildcards(self._h, blob, offs.ctypes.data_as(C.POINTER(C.c_int64)), n,
+                                                C.byref(mo), C.byref(ti)))
+        off = np.ctypeslib.as_array(mo, (n + 1,)).copy()
+        total = int(off[n])
+        ids = np.ctypeslib.as_array(ti, (total,)).copy() if total else np.zeros(0, np.int32)
+        return off, ids
+
+    def expand_wildcards_device(self, patterns, stream=None):
+        """sme_index_expand_wildcards_device: (device pointer of match_off int64[n+1],
+        device pointer of term_ids int32[total], total); the arrays belong to the
+        index until its next expansion."""
+        blob, offs, n = Index._pattern_args(patterns)
+        mo, ti, tot = C.c_void_p(), C.c_void_p(), C.c_int64()
+        _check(lib().sme_index_expand_wildcards_device(self._h, blob, offs.ctypes.data_as(C.POINTER(C.c_int64)), n,
+                                                       C.c_void_p(stream or 0), C.byref(mo), C.byref(ti),
+                                                       C.byref(tot)))
+        return mo.value or 0, ti.value or 0, tot.value
+
     def reweight(self, n_global, d_df_global=None, stream=None):
         """TF-IDF weights with all-reduced N (and df) of a doc-sharded index."""
         _check(lib().sme_index_reweight(self._h, n_global, C.c_void_p(d_df_global or 0), C.c_void_p(stream or 0)))
@@ -645,6 +698,26 @@ class IntDocVectorsForwardIndex:
     def getValue(self, terms):  # noqa: N802
         ids = self.index.lookup(list(terms))
         self._terms = [int(t) for t in ids if t >= 0]  # unknown terms are skipped silently
+
+    def get_wildcard(self, words):
+        """getValue with wildcard words: a word holding '*' or '?' is lower-cased
+        (str.lower) and expanded against the vocabulary (Index.expand_wildcards);
+        the other words go through processContent and the term lookup as
+        getValue's callers send them.  The query becomes the plain terms in order,
+        then each pattern's matches in order; a term reached twice counts twice, as
+        duplicates do in sme_query_topk.  rank() then works unchanged -- an
+        expansion past the query side's limit of 1024 terms per query surfaces
+        there, as the SmeError (SME_ELIMIT) query_topk raises."""
+        words = list(words)
+        pats = [w.lower() for w in words if "*" in w or "?" in w]
+        plain = [w for w in words if not ("*" in w or "?" in w)]
+        toks = []
+        for w in plain:
+            toks.extend(self.index.ctx.process_content(w))
+        self._terms = [int(t) for t in self.index.lookup(toks) if t >= 0]
+        if pats:
+            _, ids = self.index.expand_wildcards(pats)
+            self._terms.extend(int(t) for t in ids)
 
     def rank(self, k=10):
         if not self._terms:

@@ -336,6 +336,13 @@ int sme_set_option(sme_ctx *cx, const char *name, int64_t v) {
     } else if (n == "docid_split") {
       range(0, 2);
       cx->opt_docid_split = v;
+    } else if (n == "wild_scan") {
+      range(0, 1);
+      cx->opt_wild_scan = v;
+    } else if (n == "wild_chunk") {
+      range(64, 4096);
+      if (v % 64) throw sme::Error(SME_EINVAL, "option " + n + " must be a multiple of 64");
+      cx->opt_wild_chunk = v;
     } else {
       throw sme::Error(SME_EINVAL, "unknown option " + n);
     }
@@ -695,6 +702,71 @@ int sme_lookup_terms(sme_index *ix, const uint8_t *terms, const int64_t *offs, i
     std::vector<std::vector<uint16_t>> q(n);
     for (int i = 0; i < n; i++) q[i] = utf8_to_u16(terms + offs[i], (size_t)(offs[i + 1] - offs[i]));
     sme::lookup_terms(ix, q, term_ids, ix->ctx->own_stream);
+  });
+}
+
+// wildcard expansion runs over the vocabulary of a K = 1 term index
+static void need_wildcard_index(const sme_index *ix) {
+  if (ix->job != 0) throw sme::Error(SME_EINVAL, "wildcards: a CharKGramTermIndexer output has no term vocabulary");
+  if (ix->records_only)
+    throw sme::Error(SME_EINVAL, "wildcards: records-only index (merged shard pieces): expand on the shard indexes");
+  if (ix->K != 1) throw sme::Error(SME_EINVAL, "wildcards: K = " + std::to_string(ix->K) + " index (K = 1 only)");
+}
+
+int sme_index_prepare_wildcards(sme_index *ix, void *stream, float *ms) {
+  return guard([&] {
+    if (!ix) throw sme::Error(SME_EINVAL, "null index");
+    need_wildcard_index(ix);
+    set_device(ix->ctx);
+    sme::prepare_wildcards(ix, stream_of(ix->ctx, stream));
+    if (ms) *ms = ix->wild_ms;
+  });
+}
+
+int sme_index_wildcard_stats(sme_index *ix, uint64_t *ngrams, uint64_t *npairs) {
+  return guard([&] {
+    if (!ix || !ngrams || !npairs) throw sme::Error(SME_EINVAL, "null argument");
+    need_wildcard_index(ix);
+    set_device(ix->ctx);
+    sme::prepare_wildcards(ix, ix->ctx->own_stream);
+    *ngrams = (uint64_t)ix->wild_G;
+    *npairs = (uint64_t)ix->wild_pairs;
+  });
+}
+
+int sme_index_expand_wildcards_device(sme_index *ix, const uint8_t *patterns, const int64_t *offs, int n, void *stream,
+                                      const int64_t **d_match_off, const int32_t **d_term_ids, int64_t *total) {
+  return guard([&] {
+    if (!ix || !d_match_off || !d_term_ids || n < 0 || (n > 0 && !offs) || (n > 0 && !patterns && offs[n] > offs[0]))
+      throw sme::Error(SME_EINVAL, "bad argument");
+    need_wildcard_index(ix);
+    set_device(ix->ctx);
+    sme::expand_wildcards(ix, patterns, offs, n, stream_of(ix->ctx, stream));
+    *d_match_off = (const int64_t *)ix->d_wx_off.p;
+    *d_term_ids = (const int32_t *)ix->d_wx_ids.p;
+    if (total) *total = ix->wx_total;
+  });
+}
+
+int sme_index_expand_wildcards(sme_index *ix, const uint8_t *patterns, const int64_t *offs, int n,
+                               const int64_t **match_off, const int32_t **term_ids) {
+  return guard([&] {
+    if (!ix || !match_off || !term_ids || n < 0 || (n > 0 && !offs) || (n > 0 && !patterns && offs[n] > offs[0]))
+      throw sme::Error(SME_EINVAL, "bad argument");
+    need_wildcard_index(ix);
+    set_device(ix->ctx);
+    hipStream_t st = ix->ctx->own_stream;
+    sme::expand_wildcards(ix, patterns, offs, n, st);
+    ix->h_wx_off.resize((size_t)n + 1);
+    ix->h_wx_ids.resize((size_t)ix->wx_total + 1);  // (never an empty vector: data() stays a valid pointer)
+    SME_HIP(hipMemcpyAsync(ix->h_wx_off.data(), ix->d_wx_off.p, ((size_t)n + 1) * sizeof(int64_t),
+                           hipMemcpyDeviceToHost, st));
+    if (ix->wx_total)
+      SME_HIP(hipMemcpyAsync(ix->h_wx_ids.data(), ix->d_wx_ids.p, (size_t)ix->wx_total * sizeof(int32_t),
+                             hipMemcpyDeviceToHost, st));
+    SME_HIP(hipStreamSynchronize(st));
+    *match_off = ix->h_wx_off.data();
+    *term_ids = ix->h_wx_ids.data();
   });
 }
 

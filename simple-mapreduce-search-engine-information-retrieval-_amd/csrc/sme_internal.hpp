@@ -66,6 +66,8 @@ struct sme_ctx {
   int64_t opt_win_sample = 1;     // "win_sample": 1 = every 8th window first, thresholds raised, then the rest
   int64_t opt_win_stage_min = 0;   // "win_stage_min": windows of the first stage (at least; the stage count follows; 0 = auto)
   int64_t opt_query_budget = 0;  // "query_table_budget": per-batch skip-table bytes (0: a quarter of free HBM)
+  int64_t opt_wild_scan = 0;      // "wild_scan": 1 = every wildcard pattern takes the whole vocabulary as candidates
+  int64_t opt_wild_chunk = 1024;  // "wild_chunk": wildcard candidates per workgroup (64..4096, multiples of 64)
   int64_t opt_corpus_keep = int64_t(16) << 30;  // "corpus_keep_bytes": host-corpus builds keep their device copy
                                                 // (no hipMalloc next build) only up to this size
   // pinned host staging of device -> host record copies into pageable caller
@@ -143,13 +145,30 @@ struct sme_index {
   int64_t q_T = 0, q_H = 0, q_div = -1;
   bool q_ready = false;
   float q_prep_ms = 0.0f;
+  // wildcard expansion (sme_wild.hip): the vocabulary's character-trigram table,
+  // built on first use and kept (it depends on the term strings only) ...
+  sme::DevBuf d_wkeys;   // uint64 [G]      distinct trigram keys, ascending
+  sme::DevBuf d_wgoff;   // int32 [G + 1]   CSR offsets into d_wgterm
+  sme::DevBuf d_wgterm;  // int32 [pairs]   term ids per key, ascending
+  int64_t wild_G = 0, wild_pairs = 0;
+  bool wild_ready = false;
+  float wild_ms = 0.0f;
+  // ... and the last expansion: its outputs (owned by the index until the next
+  // one), the uploaded batch, and scratch per pattern and per candidate chunk
+  sme::DevBuf d_wx_off;  // int64 [n + 1]   match offsets
+  sme::DevBuf d_wx_ids;  // int32 [total]   matching term ids
+  sme::DevBuf d_wx_in, d_wx_plan, d_wx_choff, d_wx_moff, d_wx_scan;
+  int64_t wx_total = 0;
+  std::vector<int64_t> h_wx_off;
+  std::vector<int32_t> h_wx_ids;
   // stage timings of the build that produced this index (ms)
   std::vector<std::pair<std::string, float>> profile;
   ~sme_index() { ctx->live_indexes--; }  // members (pooled buffers) are released after this body
   explicit sme_index(sme_ctx *c) : ctx(c) {
     c->live_indexes++;
     for (sme::DevBuf *b : {&d_term_off, &d_term_chars, &d_off, &d_docno_d, &d_tf_d, &d_w, &d_idf, &d_lut, &d_gram, &d_docno_o,
-                           &d_tf_o, &d_rec_docno, &d_rec_first, &d_ser, &d_hrow_of, &d_heavy, &d_spk})
+                           &d_tf_o, &d_rec_docno, &d_rec_first, &d_ser, &d_hrow_of, &d_heavy, &d_spk, &d_wkeys, &d_wgoff,
+                           &d_wgterm, &d_wx_off, &d_wx_ids, &d_wx_in, &d_wx_plan, &d_wx_choff, &d_wx_moff, &d_wx_scan})
       b->pool = &c->pool;
   }
 };
@@ -288,4 +307,8 @@ void merge_rows(const double *s, const int32_t *d, const uint32_t *t, int64_t ro
 int64_t count_shared_keys(sme_ctx *cx, const uint64_t *rows, int64_t n, hipStream_t st);
 void lookup_terms(sme_index *ix, const std::vector<std::vector<uint16_t>> &terms, int32_t *ids,
                   hipStream_t st);
+// wildcard expansion (sme_wild.hip): the vocabulary's trigram table (built once),
+// and a batch of n UTF-8 patterns -> ix->d_wx_off / d_wx_ids / wx_total
+void prepare_wildcards(sme_index *ix, hipStream_t st);
+void expand_wildcards(sme_index *ix, const uint8_t *patterns, const int64_t *offs, int n, hipStream_t st);
 }  // namespace sme
