@@ -139,7 +139,10 @@ void sme_destroy(sme_ctx *ctx);
  *                   budget of sme_index_prepare_queries (1/4 of free HBM)
  *   "wild_scan"     wildcard expansion: 0 (default) candidates from the trigram table, 1 every
  *                   pattern takes the whole vocabulary as candidates
- *   "wild_chunk"    wildcard candidates per workgroup, 64..4096 in multiples of 64 (default 1024)
+ *   "wild_chunk"    wildcard candidates per workgroup, 64..4096 in multiples of 64 (default 1024);
+ *                   spelling suggestions cut their candidates by the same option
+ *   "fuzzy_scan"    spelling suggestions: 0 (default) candidates from the trigram table, 1 every
+ *                   word takes the whole vocabulary as candidates
  * Unknown names and out-of-range values are SME_EINVAL. */
 int sme_set_option(sme_ctx *ctx, const char *name, int64_t value);
 
@@ -318,6 +321,44 @@ int sme_index_expand_wildcards(sme_index *ix, const uint8_t *patterns, const int
 int sme_index_expand_wildcards_device(sme_index *ix, const uint8_t *patterns, const int64_t *offs, int n,
                                       void *stream, const int64_t **d_match_off, const int32_t **d_term_ids,
                                       int64_t *total);
+
+/* Spelling suggestions (no reference counterpart: a word sme_lookup_terms does
+ * not know comes back -1 and getValue drops it silently).  words / offs delimit n
+ * UTF-8 words on the host as sme_index_expand_wildcards takes patterns, decoded
+ * by the same strict decoder: malformed UTF-8 is SME_EINVAL (the message names
+ * the word's index).  No unit is a metacharacter here ('*' and '?' are ordinary
+ * units) and there is no case folding.  A word has at most 64 UTF-16 units; more
+ * is SME_ELIMIT (the message names the word).  The distance is Levenshtein's over
+ * UTF-16 units as String sees them: insert, delete, substitute one unit at cost 1
+ * each, no transposition; a supplementary character is two units.  max_dist is
+ * 0..3 and m >= 0, anything else SME_EINVAL; max_dist == 0 agrees with
+ * sme_lookup_terms.  Word i's result is the terms t with dist(word i, t) <=
+ * max_dist, ordered by (distance asc, df desc, term id asc) -- df the term's
+ * posting count (true_df of sme_index_csr) -- and cut to its first m entries
+ * (m == 0: no cut): term_ids[sug_off[i] .. sug_off[i + 1]), dist[] parallel to
+ * term_ids[], n + 1 offsets, owned by the index until the next suggestion call on
+ * it (host memory from the host entry; device memory from the device entry, with
+ * *total = sug_off[n], total may be NULL).  n == 0 is valid; 2^31 or more matches
+ * in a batch BEFORE the cut are SME_ELIMIT.  Candidates come from the wildcard
+ * trigram table (built on first use by this call or by
+ * sme_index_prepare_wildcards; sme_index_reweight leaves it alone): a term within
+ * distance d of a word misses at most 3d of the word's distinct windows, so the
+ * union of the posting lists of the 3d + 1 distinct windows with the shortest
+ * lists holds every match, and a word with fewer distinct windows (short words,
+ * the empty word) takes the whole vocabulary; every candidate is verified by a
+ * bit-parallel edit distance, so the candidate source never changes a result.  A
+ * suggestion call leaves the buffers of the last wildcard expansion alone, and
+ * the other way round.  sme_index_suggest_stats reports on the last suggestion
+ * call on the index: the words that took the whole vocabulary as candidates, and
+ * the (word, term) pairs that reached the length test.  K = 1 term indexes only,
+ * refused as the wildcard entry points refuse (SME_EINVAL, the message says
+ * which); indexes opened with sme_index_from_records work. */
+int sme_index_suggest_terms(sme_index *ix, const uint8_t *words, const int64_t *offs, int n, int max_dist, int m,
+                            const int64_t **sug_off, const int32_t **term_ids, const uint8_t **dist);
+int sme_index_suggest_terms_device(sme_index *ix, const uint8_t *words, const int64_t *offs, int n, int max_dist,
+                                   int m, void *stream, const int64_t **d_sug_off, const int32_t **d_term_ids,
+                                   const uint8_t **d_dist, int64_t *total);
+int sme_index_suggest_stats(const sme_index *ix, uint64_t *scanned_words, uint64_t *candidates);
 
 /* Batched rank(): query q has term ids term_ids[q_offsets[q] .. q_offsets[q+1])
  * in query-token order (duplicates count twice, -1 entries are skipped; an id

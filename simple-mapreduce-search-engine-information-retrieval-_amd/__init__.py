@@ -54,6 +54,7 @@ EXPORTS = [
     "sme_topk_merge_rows", "sme_count_shared_keys", "sme_index_from_records", "sme_index_from_records_device",
     "sme_index_prepare_wildcards", "sme_index_wildcard_stats", "sme_index_expand_wildcards",
     "sme_index_expand_wildcards_device",
+    "sme_index_suggest_terms", "sme_index_suggest_terms_device", "sme_index_suggest_stats",
 ]
 
 
@@ -132,6 +133,12 @@ def lib():
     L.sme_index_expand_wildcards.argtypes = [vp, C.c_char_p, i64p, C.c_int, C.POINTER(i64p), C.POINTER(i32p)]
     L.sme_index_expand_wildcards_device.argtypes = [vp, C.c_char_p, i64p, C.c_int, vp, C.POINTER(vp), C.POINTER(vp),
                                                     i64p]
+    u8p = C.POINTER(C.c_uint8)
+    L.sme_index_suggest_terms.argtypes = [vp, C.c_char_p, i64p, C.c_int, C.c_int, C.c_int, C.POINTER(i64p),
+                                          C.POINTER(i32p), C.POINTER(u8p)]
+    L.sme_index_suggest_terms_device.argtypes = [vp, C.c_char_p, i64p, C.c_int, C.c_int, C.c_int, vp, C.POINTER(vp),
+                                                 C.POINTER(vp), C.POINTER(vp), i64p]
+    L.sme_index_suggest_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     _lib = L
     return L
 
@@ -535,6 +542,41 @@ class Index:
                                                        C.byref(tot)))
         return mo.value or 0, ti.value or 0, tot.value
 
+    def suggest_terms(self, words, max_dist=2, m=10):
+        """sme_index_suggest_terms: words (str, or bytes of UTF-8) -> (sug_off
+        int64[n+1], term_ids int32, dist uint8); word i's suggestions are
+        term_ids[sug_off[i]:sug_off[i+1]], the terms within max_dist (0..3) unit
+        edits of it ordered by (distance asc, df desc, term id asc) and cut to the
+        first m (0: no cut); dist runs parallel to term_ids (include/sme.h)."""
+        blob, offs, n = Index._pattern_args(words)
+        so, ti, di = C.POINTER(C.c_int64)(), C.POINTER(C.c_int32)(), C.POINTER(C.c_uint8)()
+        _check(lib().sme_index_suggest_terms(self._h, blob, offs.ctypes.data_as(C.POINTER(C.c_int64)), n,
+                                             int(max_dist), int(m), C.byref(so), C.byref(ti), C.byref(di)))
+        off = np.ctypeslib.as_array(so, (n + 1,)).copy()
+        total = int(off[n])
+        ids = np.ctypeslib.as_array(ti, (total,)).copy() if total else np.zeros(0, np.int32)
+        dist = np.ctypeslib.as_array(di, (total,)).copy() if total else np.zeros(0, np.uint8)
+        return off, ids, dist
+
+    def suggest_terms_device(self, words, max_dist=2, m=10, stream=None):
+        """sme_index_suggest_terms_device: (device pointer of sug_off int64[n+1],
+        of term_ids int32[total], of dist uint8[total], total); the arrays belong
+        to the index until its next suggestion call."""
+        blob, offs, n = Index._pattern_args(words)
+        so, ti, di, tot = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int64()
+        _check(lib().sme_index_suggest_terms_device(self._h, blob, offs.ctypes.data_as(C.POINTER(C.c_int64)), n,
+                                                    int(max_dist), int(m), C.c_void_p(stream or 0), C.byref(so),
+                                                    C.byref(ti), C.byref(di), C.byref(tot)))
+        return so.value or 0, ti.value or 0, di.value or 0, tot.value
+
+    def suggest_stats(self):
+        """(scanned_words, candidates) of the last suggestion call: the words that
+        took the whole vocabulary as candidates, and the (word, term) pairs that
+        reached the length test."""
+        a, b = C.c_uint64(), C.c_uint64()
+        _check(lib().sme_index_suggest_stats(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
     def reweight(self, n_global, d_df_global=None, stream=None):
         """TF-IDF weights with all-reduced N (and df) of a doc-sharded index."""
         _check(lib().sme_index_reweight(self._h, n_global, C.c_void_p(d_df_global or 0), C.c_void_p(stream or 0)))
@@ -718,6 +760,29 @@ class IntDocVectorsForwardIndex:
         if pats:
             _, ids = self.index.expand_wildcards(pats)
             self._terms.extend(int(t) for t in ids)
+
+    def get_corrected(self, words, max_dist=2):
+        """getValue with spelling correction: every word goes through
+        processContent; a token the lookup knows is kept, an unknown one is
+        replaced by its best suggestion (Index.suggest_terms with m = 1: the
+        nearest term within max_dist unit edits, the most frequent among equals)
+        if there is one and skipped as getValue skips it otherwise.  Sets the
+        query terms for rank() and returns the replacements made, a list of
+        (token, replacement term string)."""
+        toks = []
+        for w in words:
+            toks.extend(self.index.ctx.process_content(w))
+        ids = [int(t) for t in self.index.lookup(toks)]
+        unknown = [i for i, t in enumerate(ids) if t < 0]
+        made = []
+        if unknown:
+            off, sug, _ = self.index.suggest_terms([toks[i] for i in unknown], max_dist, 1)
+            for j, i in enumerate(unknown):
+                if off[j + 1] > off[j]:
+                    ids[i] = int(sug[off[j]])
+                    made.append((toks[i], self.index.term(ids[i])))
+        self._terms = [t for t in ids if t >= 0]
+        return made
 
     def rank(self, k=10):
         if not self._terms:

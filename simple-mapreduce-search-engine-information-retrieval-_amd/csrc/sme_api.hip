@@ -343,6 +343,9 @@ int sme_set_option(sme_ctx *cx, const char *name, int64_t v) {
       range(64, 4096);
       if (v % 64) throw sme::Error(SME_EINVAL, "option " + n + " must be a multiple of 64");
       cx->opt_wild_chunk = v;
+    } else if (n == "fuzzy_scan") {
+      range(0, 1);
+      cx->opt_fuzzy_scan = v;
     } else {
       throw sme::Error(SME_EINVAL, "unknown option " + n);
     }
@@ -767,6 +770,67 @@ int sme_index_expand_wildcards(sme_index *ix, const uint8_t *patterns, const int
     SME_HIP(hipStreamSynchronize(st));
     *match_off = ix->h_wx_off.data();
     *term_ids = ix->h_wx_ids.data();
+  });
+}
+
+// spelling suggestions run over the same vocabulary, with the same refusals
+static void need_suggest_args(const sme_index *ix, const uint8_t *words, const int64_t *offs, int n, int max_dist,
+                              int m) {
+  if (!ix || n < 0 || (n > 0 && !offs) || (n > 0 && !words && offs[n] > offs[0]))
+    throw sme::Error(SME_EINVAL, "bad argument");
+  if (max_dist < 0 || max_dist > 3) throw sme::Error(SME_EINVAL, "suggestions: max_dist must be 0..3");
+  if (m < 0) throw sme::Error(SME_EINVAL, "suggestions: m must be >= 0");
+  if (ix->job != 0) throw sme::Error(SME_EINVAL, "suggestions: a CharKGramTermIndexer output has no term vocabulary");
+  if (ix->records_only)
+    throw sme::Error(SME_EINVAL, "suggestions: records-only index (merged shard pieces): ask the shard indexes");
+  if (ix->K != 1) throw sme::Error(SME_EINVAL, "suggestions: K = " + std::to_string(ix->K) + " index (K = 1 only)");
+}
+
+int sme_index_suggest_terms_device(sme_index *ix, const uint8_t *words, const int64_t *offs, int n, int max_dist, int m,
+                                   void *stream, const int64_t **d_sug_off, const int32_t **d_term_ids,
+                                   const uint8_t **d_dist, int64_t *total) {
+  return guard([&] {
+    if (!d_sug_off || !d_term_ids || !d_dist) throw sme::Error(SME_EINVAL, "null argument");
+    need_suggest_args(ix, words, offs, n, max_dist, m);
+    set_device(ix->ctx);
+    sme::suggest_terms(ix, words, offs, n, max_dist, m, stream_of(ix->ctx, stream));
+    *d_sug_off = (const int64_t *)ix->d_fz_off.p;
+    *d_term_ids = (const int32_t *)ix->d_fz_ids.p;
+    *d_dist = (const uint8_t *)ix->d_fz_dist.p;
+    if (total) *total = ix->fz_total;
+  });
+}
+
+int sme_index_suggest_terms(sme_index *ix, const uint8_t *words, const int64_t *offs, int n, int max_dist, int m,
+                            const int64_t **sug_off, const int32_t **term_ids, const uint8_t **dist) {
+  return guard([&] {
+    if (!sug_off || !term_ids || !dist) throw sme::Error(SME_EINVAL, "null argument");
+    need_suggest_args(ix, words, offs, n, max_dist, m);
+    set_device(ix->ctx);
+    hipStream_t st = ix->ctx->own_stream;
+    sme::suggest_terms(ix, words, offs, n, max_dist, m, st);
+    const size_t tot = (size_t)ix->fz_total;
+    ix->h_fz_off.resize((size_t)n + 1);
+    ix->h_fz_ids.resize(tot + 1);  // (never an empty vector: data() stays a valid pointer)
+    ix->h_fz_dist.resize(tot + 1);
+    SME_HIP(hipMemcpyAsync(ix->h_fz_off.data(), ix->d_fz_off.p, ((size_t)n + 1) * sizeof(int64_t),
+                           hipMemcpyDeviceToHost, st));
+    if (tot) {
+      SME_HIP(hipMemcpyAsync(ix->h_fz_ids.data(), ix->d_fz_ids.p, tot * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+      SME_HIP(hipMemcpyAsync(ix->h_fz_dist.data(), ix->d_fz_dist.p, tot, hipMemcpyDeviceToHost, st));
+    }
+    SME_HIP(hipStreamSynchronize(st));
+    *sug_off = ix->h_fz_off.data();
+    *term_ids = ix->h_fz_ids.data();
+    *dist = ix->h_fz_dist.data();
+  });
+}
+
+int sme_index_suggest_stats(const sme_index *ix, uint64_t *scanned_words, uint64_t *candidates) {
+  return guard([&] {
+    if (!ix || !scanned_words || !candidates) throw sme::Error(SME_EINVAL, "null argument");
+    *scanned_words = ix->fz_scanned;
+    *candidates = ix->fz_cands;
   });
 }
 

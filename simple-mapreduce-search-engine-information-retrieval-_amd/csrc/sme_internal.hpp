@@ -68,6 +68,7 @@ struct sme_ctx {
   int64_t opt_query_budget = 0;  // "query_table_budget": per-batch skip-table bytes (0: a quarter of free HBM)
   int64_t opt_wild_scan = 0;      // "wild_scan": 1 = every wildcard pattern takes the whole vocabulary as candidates
   int64_t opt_wild_chunk = 1024;  // "wild_chunk": wildcard candidates per workgroup (64..4096, multiples of 64)
+  int64_t opt_fuzzy_scan = 0;      // "fuzzy_scan": 1 = every suggestion word takes the whole vocabulary as candidates
   int64_t opt_corpus_keep = int64_t(16) << 30;  // "corpus_keep_bytes": host-corpus builds keep their device copy
                                                 // (no hipMalloc next build) only up to this size
   // pinned host staging of device -> host record copies into pageable caller
@@ -161,6 +162,17 @@ struct sme_index {
   int64_t wx_total = 0;
   std::vector<int64_t> h_wx_off;
   std::vector<int32_t> h_wx_ids;
+  // spelling suggestions (sme_fuzzy.hip): the last call's outputs (owned by the
+  // index until the next one; its temporaries are pooled blocks of the call) and
+  // what it counted
+  sme::DevBuf d_fz_off;   // int64 [n + 1]  suggestion offsets
+  sme::DevBuf d_fz_ids;   // int32 [total]  term ids
+  sme::DevBuf d_fz_dist;  // u8 [total]     their distances
+  int64_t fz_total = 0;
+  uint64_t fz_scanned = 0, fz_cands = 0;  // words that took the whole vocabulary; (word, term) pairs length-tested
+  std::vector<int64_t> h_fz_off;
+  std::vector<int32_t> h_fz_ids;
+  std::vector<uint8_t> h_fz_dist;
   // stage timings of the build that produced this index (ms)
   std::vector<std::pair<std::string, float>> profile;
   ~sme_index() { ctx->live_indexes--; }  // members (pooled buffers) are released after this body
@@ -168,7 +180,8 @@ struct sme_index {
     c->live_indexes++;
     for (sme::DevBuf *b : {&d_term_off, &d_term_chars, &d_off, &d_docno_d, &d_tf_d, &d_w, &d_idf, &d_lut, &d_gram, &d_docno_o,
                            &d_tf_o, &d_rec_docno, &d_rec_first, &d_ser, &d_hrow_of, &d_heavy, &d_spk, &d_wkeys, &d_wgoff,
-                           &d_wgterm, &d_wx_off, &d_wx_ids, &d_wx_in, &d_wx_plan, &d_wx_choff, &d_wx_moff, &d_wx_scan})
+                           &d_wgterm, &d_wx_off, &d_wx_ids, &d_wx_in, &d_wx_plan, &d_wx_choff, &d_wx_moff, &d_wx_scan, &d_fz_off,
+                           &d_fz_ids, &d_fz_dist})
       b->pool = &c->pool;
   }
 };
@@ -311,4 +324,9 @@ void lookup_terms(sme_index *ix, const std::vector<std::vector<uint16_t>> &terms
 // and a batch of n UTF-8 patterns -> ix->d_wx_off / d_wx_ids / wx_total
 void prepare_wildcards(sme_index *ix, hipStream_t st);
 void expand_wildcards(sme_index *ix, const uint8_t *patterns, const int64_t *offs, int n, hipStream_t st);
+// spelling suggestions (sme_fuzzy.hip): a batch of n UTF-8 words -> per word the
+// terms within max_dist edits, ordered and cut to m: ix->d_fz_off / d_fz_ids /
+// d_fz_dist / fz_total, and the call's counts fz_scanned / fz_cands
+void suggest_terms(sme_index *ix, const uint8_t *words, const int64_t *offs, int n, int max_dist, int m,
+                   hipStream_t st);
 }  // namespace sme
