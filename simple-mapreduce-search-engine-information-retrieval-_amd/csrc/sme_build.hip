@@ -2422,6 +2422,12 @@ struct AggIn {
   int64_t *dcnt = nullptr;
   int64_t *big_out = nullptr;
   unsigned long long *nbig = nullptr;
+  // packed single-pass form (rec_val != nullptr, and then v32 == nullptr): one
+  // word per pair in the region, term | tf << tf_shift (tf_shift = the term
+  // sort's key width; the tf field above it holds any tf < F), and record i's
+  // (docno - dmin) * F in rec_val[i]; the sort's first pass adds the two
+  uint32_t *rec_val = nullptr;
+  int tf_shift = 0;
   // K6b split (single-pass form only): a pair whose term code has kDocCode goes to
   // dk_rec[i] / dv_rec[i] (record i in docno order) instead of the region; a
   // second one in the same record sets *dbad
@@ -2657,18 +2663,25 @@ __global__ __launch_bounds__(kAggNT) void k_agg_w(AggIn in, int64_t nR, int32_t 
           in.dv_rec[i] = vdoc + (uint32_t)c;
         } else {
           const int64_t o = base + __popcll(m & ((1ull << lane) - 1ull));
-          st_stream(p_term + o, (uint32_t)key);
-          if (in.v32)
-            st_stream(in.v32 + o, vdoc + (uint32_t)c);
-          else
-            p_val[o] = dn | (uint32_t)c;
+          if (in.rec_val) {
+            st_stream(p_term + o, (uint32_t)key | (uint32_t)c << in.tf_shift);
+          } else {
+            st_stream(p_term + o, (uint32_t)key);
+            if (in.v32)
+              st_stream(in.v32 + o, vdoc + (uint32_t)c);
+            else
+              p_val[o] = dn | (uint32_t)c;
+          }
         }
         if (fused) wmax = max(wmax, (uint32_t)c);
       }
       if (in.dk_rec) nd += __popcll((uint64_t)__ballot(isd));
       base += __popcll(m);
     }
-    if (fused && lane == 0) in.dcnt[i] = d - nd;
+    if (fused && lane == 0) {
+      in.dcnt[i] = d - nd;
+      if (in.rec_val) in.rec_val[i] = vdoc;
+    }
     if (nd > 1 && lane == 0) *in.dbad = 1ull;  // two docid terms' pairs: merged ids (K6b fallback)
     wave_sync_lds();
   }
@@ -2727,15 +2740,22 @@ __global__ __launch_bounds__(kAggNT) void k_agg_big(AggIn in, const int64_t *big
       int32_t tot;
       int32_t o = block_excl_sum<kAggNT, int32_t>(key >= 0 ? 1 : 0, sc32, &tot);
       if (key >= 0) {
-        p_term[base + o] = (uint32_t)key;
-        if (in.v32)
-          in.v32[base + o] = (uint32_t)(((int64_t)in.docno[r] - in.dmin) * (int64_t)in.F + cnt[k]);
-        else
-          p_val[base + o] = ((uint64_t)(uint32_t)in.docno[r] << 32) | (uint32_t)cnt[k];
+        if (pass == 2 && in.rec_val) {
+          p_term[base + o] = (uint32_t)key | (uint32_t)cnt[k] << in.tf_shift;
+        } else {
+          p_term[base + o] = (uint32_t)key;
+          if (in.v32)
+            in.v32[base + o] = (uint32_t)(((int64_t)in.docno[r] - in.dmin) * (int64_t)in.F + cnt[k]);
+          else
+            p_val[base + o] = ((uint64_t)(uint32_t)in.docno[r] << 32) | (uint32_t)cnt[k];
+        }
       }
       base += tot;
     }
-    if (pass == 2 && threadIdx.x == 0) in.dcnt[i] = base - pair_off[i];
+    if (pass == 2 && threadIdx.x == 0) {
+      in.dcnt[i] = base - pair_off[i];
+      if (in.rec_val) in.rec_val[i] = (uint32_t)(((int64_t)in.docno[r] - in.dmin) * (int64_t)in.F);
+    }
     __syncthreads();
   }
 }
@@ -4273,7 +4293,10 @@ vocab_again:  // (a docid term equal to a word term: the general path, from here
     if (Pb > 0 && Pb < (1ll << 32) && D * Fq < (1ull << 32) && tbits0 + bits_for(Fq - 1) <= 32) {
       fused = true;
       p_term = W[W_PTERM].as<uint32_t>(Pb + 1);
-      ai.v32 = W[W_PVAL].as<uint32_t>(Pb + 1);
+      // one packed word per pair (term | tf << key width: the condition above is
+      // that they fit) and one base value per record: no second region buffer
+      ai.rec_val = W[W_PREC].as<uint32_t>(nR + 1);
+      ai.tf_shift = tbits0;
       ai.dmin = h_drange[0];
       ai.F = (uint32_t)Fq;
       ai.reg_off = reg_off;
@@ -4318,6 +4341,13 @@ vocab_again:  // (a docid term equal to a word term: the general path, from here
         ai.dk_rec = nullptr;
         ai.dv_rec = nullptr;
         ai.dbad = nullptr;
+        // the merged ids are wider than the word ranks: where they leave the tf no
+        // room in the word, the regions take separate value words
+        ai.tf_shift = bits_for((uint64_t)std::max<int64_t>(Vi, 1));
+        if (ai.tf_shift + bits_for(Fq - 1) > 32) {
+          ai.rec_val = nullptr;
+          ai.v32 = W[W_PVAL].as<uint32_t>(Pb + 1);
+        }
         run_fused();
       }
       // exact pair offsets of the records (docno order)
@@ -4549,7 +4579,7 @@ vocab_again:  // (a docid term equal to a word term: the general path, from here
   bool packed = false;
   int64_t dmin = 0;
   uint32_t F = 0;
-  if (ai.v32 != nullptr) {  // emitted packed by the aggregation (see want_packed)
+  if (ai.v32 != nullptr || ai.rec_val != nullptr) {  // emitted packed by the aggregation (see want_packed)
     max_tf = std::max<int32_t>(1, h_mtf);
     packed = true;
     dmin = ai.dmin;
@@ -4575,8 +4605,17 @@ vocab_again:  // (a docid term equal to a word term: the general path, from here
   std::vector<double> early_lut;  // the fused weight pass's LUT (outlives its async upload)
   bool weights_fused = false;
   if (packed) {
+    // digit width (sort_digit_bits; 0 = auto): 11, or 8 past 2^30 pairs -- a pass's
+    // per-(tile, digit) counts grow with the pairs, and 2048 digits over an 8192-pair
+    // tile leave 4-pair runs to scatter (c4 shard, 22-bit keys: two 11-bit passes
+    // 34.5 ms, three of <= 8 bits 30.9 ms; c2 / c5 keep 11)
+    const int sort_bits = cx->opt_sort_bits > 0 ? (int)cx->opt_sort_bits : (Pw > (int64_t(1) << 30) ? 8 : 11);
     uint32_t *v32 = ai.v32;
-    if (v32 == nullptr) {
+    if (ai.rec_val != nullptr) {
+      // packed words: the first pass reads no value buffer, and only a third pass
+      // writes this one
+      if (term_sort_passes(tbits, sort_bits) >= 3) v32 = W[W_PVAL].as<uint32_t>(P + 1);
+    } else if (v32 == nullptr) {
       v32 = reinterpret_cast<uint32_t *>(W[W_T1].as<uint64_t>(P + 1));
       hipLaunchKernelGGL(k_pack_pairs, dim3(grid_for(P)), dim3(256), 0, st, p_val, P, dmin, F, v32);
     }
@@ -4598,13 +4637,9 @@ vocab_again:  // (a docid term equal to a word term: the general path, from here
       weights_fused = true;
     }
     const double idf_r = log10((double)(std::max<int64_t>(nR, 0) / 1));
-    // digit width (sort_digit_bits; 0 = auto): 11, or 8 past 2^30 pairs -- a pass's
-    // per-(tile, digit) counts grow with the pairs, and 2048 digits over an 8192-pair
-    // tile leave 4-pair runs to scatter (c4 shard, 22-bit keys: two 11-bit passes
-    // 34.5 ms, three of <= 8 bits 30.9 ms; c2 / c5 keep 11)
-    const int sort_bits = cx->opt_sort_bits > 0 ? (int)cx->opt_sort_bits : (Pw > (int64_t(1) << 30) ? 8 : 11);
     key_s = term_sort(p_term, v32, key_s, v32s, sort_nrec, sort_reg, sort_xoff, Pw, tbits, dmin, F, docno_d, tf_d, rscr,
-                      st, wf ? (const double *)ix->d_lut.p : nullptr, idf_r, wf, sort_bits, xw, P);
+                      st, wf ? (const double *)ix->d_lut.p : nullptr, idf_r, wf, sort_bits, xw, P, ai.rec_val,
+                      ai.tf_shift);
     off = ix->d_off.as<int64_t>(Vi + 1);
     SME_HIP(hipMemsetAsync(off, 0, (Vi + 1) * sizeof(int64_t), st));
     if (!split) {
@@ -4744,14 +4779,17 @@ vocab_again:  // (a docid term equal to a word term: the general path, from here
     SME_CHECK_LAUNCH();
   } else if (PP > 0) {  // (aux_join: st waits for the auxiliary stream here)
     const int tfb = bits_for((uint64_t)max_tf);
-    if (tbits + tfb <= 32) {  // u32 composite (term, tf desc)
+    // (the sorted keys are merged term ids: after the K6b split they are wider than
+    // the term sort's word ranks)
+    const int kbits = bits_for((uint64_t)std::max<int64_t>(Vi, 1));
+    if (kbits + tfb <= 32) {  // u32 composite (term, tf desc)
       const uint32_t tfmask = (uint32_t)((1ull << tfb) - 1);
       uint32_t *ck = reinterpret_cast<uint32_t *>(W[W_PVAL].as<uint64_t>(PP)), *ck2 = W[W_T2].as<uint32_t>(PP);
       hipLaunchKernelGGL(k_composite32, dim3(grid_for(PP)), dim3(256), 0, st, key_s, tf_d, PP, tfb, tfmask, ck);
       // (docno_d stays intact: the sort's values start from a copy)
       uint32_t *dv = W[W_T3].as<uint32_t>(PP);
       SME_HIP(hipMemcpyAsync(dv, docno_d, (size_t)PP * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-      sort_pairs<uint32_t>(ck, ck2, dv, reinterpret_cast<uint32_t *>(docno_o), PP, tbits + tfb, cx->ws[122], st);
+      sort_pairs<uint32_t>(ck, ck2, dv, reinterpret_cast<uint32_t *>(docno_o), PP, kbits + tfb, cx->ws[122], st);
       hipLaunchKernelGGL(k_composite32_tf, dim3(grid_for(PP)), dim3(256), 0, st, ck2, PP, tfmask, tf_o);
     } else {
       const uint64_t tfmask = (1ull << tfb) - 1;
@@ -4759,7 +4797,7 @@ vocab_again:  // (a docid term equal to a word term: the general path, from here
       hipLaunchKernelGGL(k_composite, dim3(grid_for(PP)), dim3(256), 0, st, key_s, tf_d, PP, tfb, tfmask, ck);
       uint32_t *dv = W[W_T3].as<uint32_t>(PP);
       SME_HIP(hipMemcpyAsync(dv, docno_d, (size_t)PP * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-      sort_pairs<uint64_t>(ck, ck2, dv, reinterpret_cast<uint32_t *>(docno_o), PP, tbits + tfb, cx->ws[122], st);
+      sort_pairs<uint64_t>(ck, ck2, dv, reinterpret_cast<uint32_t *>(docno_o), PP, kbits + tfb, cx->ws[122], st);
       hipLaunchKernelGGL(k_composite_tf, dim3(grid_for(PP)), dim3(256), 0, st, ck2, PP, tfmask, tf_o);
     }
     SME_CHECK_LAUNCH();

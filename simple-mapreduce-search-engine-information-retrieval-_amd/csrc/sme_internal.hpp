@@ -251,7 +251,12 @@ void chargram_stage(sme_ctx *cx, sme_index *ix, const int32_t *tstream, int64_t 
 uint32_t *term_sort(uint32_t *k0, uint32_t *v0, uint32_t *k1, uint32_t *v1, int64_t nrec, const int64_t *reg,
                     const int64_t *xoff, int64_t P, int bits, int64_t dmin, uint32_t F, int32_t *docno, int32_t *tf,
                     uint32_t *counts, hipStream_t st, const double *lut = nullptr, double idf = 0.0,
-                    double *w = nullptr, int maxbits = 11, const uint2 *xw = nullptr, int64_t Pout = 0);
+                    double *w = nullptr, int maxbits = 11, const uint2 *xw = nullptr, int64_t Pout = 0,
+                    const uint32_t *rec_val = nullptr, int tf_shift = 0);
+// (rec_val != nullptr, gather mode: the regions hold one packed word per pair,
+// term | tf << tf_shift, and rec_val[i] = record i's base value; v0 is then read
+// by no pass, and written only when there are three passes or more)
+int term_sort_passes(int bits, int maxbits);
 size_t term_sort_scratch(int64_t P);
 // stable LSD radix sort of (key, u32 value) pairs by the key's low `bits` bits
 // (sme_sort.hip; K = uint32_t or uint64_t); ping-pongs between (k0, v0) and

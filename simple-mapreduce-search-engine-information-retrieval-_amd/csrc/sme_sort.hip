@@ -20,7 +20,9 @@
 //                LDS in that order, and writes them out as contiguous runs
 //                per digit (offset(tile, digit) + slot - digit's first slot).
 // The last pass writes the sorted keys and unpacks the packed values
-// ((docno - dmin) * F + tf) straight into the CSR's docno / tf arrays.
+// ((docno - dmin) * F + tf) straight into the CSR's docno / tf arrays.  After
+// the single-pass aggregation the first pass gathers its items from the
+// records' regions, one packed word per pair (Gather).
 #include <hip/hip_runtime.h>
 
 #include "sme_internal.hpp"
@@ -60,9 +62,15 @@ static RsGroups rs_groups(int64_t ntiles) {
 // reg[i] + (x - xoff[i]) (xoff = exclusive scan of the records' pair counts);
 // crec[c] = the record holding pair 1024 c, so a wave's walk over its 1024
 // items starts there and advances a record at a time.
+// Packed form (rval != nullptr): the region holds one word per pair,
+// term | tf << tf_shift, and rval[i] = (docno - dmin) * F of record i, so the
+// pair's key is the word's low tf_shift bits and its value rval[i] + tf; no
+// value array is read.
 struct Gather {
   const int64_t *reg, *xoff, *crec;
   int64_t nrec;
+  const uint32_t *rval;
+  int tf_shift;
 };
 __device__ __forceinline__ void gather_start(const Gather &g, int64_t x, int64_t &rec, int64_t &nx, int64_t &dl) {
   rec = g.crec[x >> 10];
@@ -80,14 +88,19 @@ __device__ __forceinline__ int64_t gather_pos(const Gather &g, int64_t x, int64_
 // A wave's 1024 items span a few records: lane j loads record rec0 + j's pair
 // start and region delta into LDS once, so the per-item walk reads LDS and the
 // item loads are not held behind dependent global loads (vmcnt is in order).
-// Walks past kGRec records fall back to the global walk.
+// Walks past kGRec records fall back to the global walk.  gv (packed form): the
+// records' base values, a third column of the table; gather_at then also gives
+// the item's record, as its distance jr from the wave's first (the base value is
+// looked up once every item load is issued: gv[jr], or rval past the table).
 constexpr int kGRec = 48;  // (LDS: two 512-thread scatter blocks per CU)
-__device__ __forceinline__ int64_t gather_table(const Gather &g, int64_t x0, int lane, int64_t *gx, int64_t *gdl) {
+__device__ __forceinline__ int64_t gather_table(const Gather &g, int64_t x0, int lane, int64_t *gx, int64_t *gdl,
+                                                uint32_t *gv = nullptr) {
   const int64_t rec0 = g.crec[x0 >> 10];
   const int64_t r = rec0 + lane;
   if (lane < kGRec) {
     gx[lane] = r <= g.nrec ? g.xoff[r] : INT64_MAX;
     gdl[lane] = r < g.nrec ? g.reg[r] - g.xoff[r] : 0;
+    if (gv) gv[lane] = r < g.nrec ? g.rval[r] : 0u;
   }
   if (lane == 0) gx[kGRec] = rec0 + kGRec <= g.nrec ? g.xoff[rec0 + kGRec] : INT64_MAX;
   __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
@@ -95,11 +108,16 @@ __device__ __forceinline__ int64_t gather_table(const Gather &g, int64_t x0, int
   return rec0;
 }
 __device__ __forceinline__ int64_t gather_at(const Gather &g, int64_t x, int &j, const int64_t *gx, const int64_t *gdl,
-                                             int64_t rec0) {
+                                             int64_t rec0, uint32_t *jr = nullptr) {
   while (j < kGRec - 1 && x >= gx[j + 1]) j++;
-  if (x < gx[j + 1]) return x + gdl[j];
+  if (x < gx[j + 1]) {
+    if (jr) *jr = (uint32_t)j;
+    return x + gdl[j];
+  }
   int64_t rec = rec0 + kGRec - 1, nx = g.xoff[rec + 1], dl = g.reg[rec] - g.xoff[rec];
-  return gather_pos(g, x, rec, nx, dl);
+  const int64_t p = gather_pos(g, x, rec, nx, dl);
+  if (jr) *jr = (uint32_t)(rec - rec0);
+  return p;
 }
 __global__ void k_rs_chunk_rec(const int64_t *__restrict__ xoff, int64_t nrec, int64_t P, int64_t *__restrict__ crec) {
   for (int64_t c = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; (c << 10) < P; c += (int64_t)gridDim.x * blockDim.x) {
@@ -241,7 +259,9 @@ __global__ __launch_bounds__(kRsNT) void k_rs_colscan(uint32_t *__restrict__ cou
   }
 }
 
-template <bool LAST>
+// (PACK: the first pass over packed words, see Gather; its own instantiation, so
+// the other passes' code is what it is without it)
+template <bool LAST, bool PACK>
 __global__ __launch_bounds__(kRsNT) void k_rs_scatter(const uint32_t *__restrict__ key, const uint32_t *__restrict__ val,
                                                       int64_t P, int shift, int nbits,
                                                       const uint32_t *__restrict__ offs, uint32_t *__restrict__ okey,
@@ -276,18 +296,40 @@ __global__ __launch_bounds__(kRsNT) void k_rs_scatter(const uint32_t *__restrict
   uint32_t k[kRsIPL], v[kRsIPL], pos[kRsIPL];
   if (g.reg != nullptr) {
     __shared__ int64_t gx_all[kRsWaves][kGRec + 1], gdl_all[kRsWaves][kGRec];
+    __shared__ uint32_t gv_all[kRsWaves][kGRec];
+    uint32_t *gv = PACK ? gv_all[w] : nullptr;
     int64_t rec0 = 0;
-    if (wb < n) rec0 = gather_table(g, t0 + wb, lane, gx_all[w], gdl_all[w]);
+    if (wb < n) rec0 = gather_table(g, t0 + wb, lane, gx_all[w], gdl_all[w], gv);
     int j = 0;
+    if (PACK) {  // packed words: key = low tf_shift bits, value = the record's base + tf
+      const uint32_t kmask = g.tf_shift >= 32 ? 0xFFFFFFFFu : (1u << g.tf_shift) - 1u;
 #pragma unroll
-    for (int s = 0; s < kRsIPL; s++) {
-      const int i = wb + s * 64 + lane;
-      k[s] = 0u;
-      v[s] = 0u;
-      if (i < n) {
-        const int64_t p = gather_at(g, t0 + i, j, gx_all[w], gdl_all[w], rec0);
-        k[s] = key[p];
-        v[s] = val[p];
+      for (int s = 0; s < kRsIPL; s++) {
+        const int i = wb + s * 64 + lane;
+        k[s] = 0u;
+        v[s] = 0u;
+        if (i < n) k[s] = key[gather_at(g, t0 + i, j, gx_all[w], gdl_all[w], rec0, &v[s])];
+      }
+      // (unpacked after the loop: a use of the word inside the branch above would
+      // make every load wait for the one before it)
+#pragma unroll
+      for (int s = 0; s < kRsIPL; s++) {
+        const uint32_t wd = k[s], jr = v[s];
+        k[s] = wd & kmask;
+        if (wb + s * 64 + lane < n)
+          v[s] = (jr < (uint32_t)kGRec ? gv[jr] : g.rval[rec0 + jr]) + (uint32_t)((uint64_t)wd >> g.tf_shift);
+      }
+    } else {
+#pragma unroll
+      for (int s = 0; s < kRsIPL; s++) {
+        const int i = wb + s * 64 + lane;
+        k[s] = 0u;
+        v[s] = 0u;
+        if (i < n) {
+          const int64_t p = gather_at(g, t0 + i, j, gx_all[w], gdl_all[w], rec0);
+          k[s] = key[p];
+          v[s] = val[p];
+        }
       }
     }
   } else {
@@ -682,31 +724,34 @@ void rs_scan(uint32_t *gsum, int64_t n, uint32_t *sums, hipStream_t st) {
 // counts: term_sort_scratch(P) bytes of scratch = ceil(P / 8192) * 2048 tile
 // counts + 2048 * 1024 (digit, group) sums + 1024 scan sums, all u32, then
 // ceil(P / 1024) + 1 int64 (gather mode's chunk table).
+// rec_val (gather mode only): the regions hold packed words, term | tf << tf_shift,
+// and rec_val[i] is record i's base value; the first pass then reads k0 alone
+// (v0 may be nullptr unless a third pass writes it: term_sort_passes).
 uint32_t *term_sort(uint32_t *k0, uint32_t *v0, uint32_t *k1, uint32_t *v1, int64_t nrec, const int64_t *reg,
                     const int64_t *xoff, int64_t P, int bits, int64_t dmin, uint32_t F, int32_t *docno, int32_t *tf,
                     uint32_t *counts, hipStream_t st, const double *lut, double idf, double *w, int maxbits,
-                    const uint2 *xw, int64_t Pout) {
+                    const uint2 *xw, int64_t Pout, const uint32_t *rec_val, int tf_shift) {
   if (P <= 0) return k0;
   if (P > 0xFFFFFFFFll) throw Error(SME_ELIMIT, "term sort of more than 2^32 pairs");
   bits = std::max(bits, 1);
   maxbits = std::min(std::max(maxbits, 1), kRsMaxBits);
-  const int npass = (bits + maxbits - 1) / maxbits;
+  const int npass = term_sort_passes(bits, maxbits);
   const int64_t ntiles = (P + kRsTile - 1) / kRsTile;
   const RsGroups rg = rs_groups(ntiles);
   const int64_t tpg = rg.tpg;
   const int G = rg.G;
   uint32_t *gsum = counts + ntiles * kRsMaxBins;
-  Gather g0{nullptr, nullptr, nullptr, 0};
+  Gather g0{nullptr, nullptr, nullptr, 0, nullptr, 0};
   if (reg != nullptr) {
     int64_t *crec = reinterpret_cast<int64_t *>(gsum + kRsMaxBins * kRsGroups + kRsScanSums);
     const int64_t nch = (P + 1023) >> 10;
     hipLaunchKernelGGL(k_rs_chunk_rec, dim3((unsigned)std::min<int64_t>((nch + 255) / 256, 4096)), dim3(256), 0, st,
                        xoff, nrec, P, crec);
-    g0 = Gather{reg, xoff, crec, nrec};
+    g0 = Gather{reg, xoff, crec, nrec, rec_val, tf_shift};
   }
   int shift = 0;
   for (int p = 0; p < npass; p++) {
-    const Gather g = p == 0 ? g0 : Gather{nullptr, nullptr, nullptr, 0};
+    const Gather g = p == 0 ? g0 : Gather{nullptr, nullptr, nullptr, 0, nullptr, 0};
 #ifdef SME_RS_LOFIRST  // (experiment: the narrower digit first)
     const int nb = (bits - shift) / (npass - p);
 #else
@@ -721,18 +766,26 @@ uint32_t *term_sort(uint32_t *k0, uint32_t *v0, uint32_t *k1, uint32_t *v1, int6
     const unsigned sgrid = (unsigned)(8 * ((ntiles + 7) / 8));  // see the XCD tile order in k_rs_scatter
     if (last && xw)  // K6b: the docid pairs' slots stay keyed 0xFFFFFFFF (k_term_offsets<true> skips them)
       SME_HIP(hipMemsetAsync(k1, 0xFF, (size_t)Pout * sizeof(uint32_t), st));
+    const bool pack = g.reg != nullptr && g.rval != nullptr;
+    auto *scatter = last ? (pack ? k_rs_scatter<true, true> : k_rs_scatter<true, false>)
+                         : (pack ? k_rs_scatter<false, true> : k_rs_scatter<false, false>);
     if (last)
-      hipLaunchKernelGGL(k_rs_scatter<true>, dim3(sgrid), dim3(kRsNT), 0, st, k0, v0, P, shift, nb, counts,
-                         k1, nullptr, docno, tf, dmin, F, g, lut, idf, w, xw);
+      hipLaunchKernelGGL(scatter, dim3(sgrid), dim3(kRsNT), 0, st, k0, v0, P, shift, nb, counts, k1, nullptr, docno, tf,
+                         dmin, F, g, lut, idf, w, xw);
     else
-      hipLaunchKernelGGL(k_rs_scatter<false>, dim3(sgrid), dim3(kRsNT), 0, st, k0, v0, P, shift, nb,
-                         counts, k1, v1, nullptr, nullptr, dmin, F, g, nullptr, 0.0, nullptr, nullptr);
+      hipLaunchKernelGGL(scatter, dim3(sgrid), dim3(kRsNT), 0, st, k0, v0, P, shift, nb, counts, k1, v1, nullptr,
+                         nullptr, dmin, F, g, nullptr, 0.0, nullptr, nullptr);
     SME_CHECK_LAUNCH();
     std::swap(k0, k1);
     std::swap(v0, v1);
     shift += nb;
   }
   return k0;
+}
+
+int term_sort_passes(int bits, int maxbits) {
+  const int mb = std::min(std::max(maxbits, 1), kRsMaxBits);
+  return (std::max(bits, 1) + mb - 1) / mb;
 }
 
 size_t term_sort_scratch(int64_t P) {
