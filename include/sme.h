@@ -489,6 +489,10 @@ int sme_merge_pieces(sme_ctx *ctx, const void *d_blobs, const uint64_t *sizes, i
  *   tok_attempts, vocab_attempts, lt_attempts   passes of the build's capacity
  *     loops (raw-vocabulary table, k_vocab's long-token / multi-term lists, the
  *     '<' list): 1 each when the first capacity held;
+ *   records_fast, records_slow   records the build tokenized with the
+ *     byte-parallel k_tok_fast and with the sequential k_tok_slow (complex
+ *     markup, or shorter than 48 bytes); their sum is the record count (like
+ *     every value here they print with six significant digits);
  *   query_overflow   k_query_win queries whose first candidate list overflowed,
  *   query_fallback   of those, the queries finally scored by the block-max sweep,
  *   query_split      1 when the batch was split by query range (table budget),

@@ -4223,6 +4223,8 @@ vocab_again:  // (a docid term equal to a word term: the general path, from here
     ix->Vt = V;
     ix->profile = prof.finish();
     ix->profile.emplace_back("tok_attempts", (float)tok_attempts);
+    ix->profile.emplace_back("records_fast", (float)nF);
+    ix->profile.emplace_back("records_slow", (float)nslow);
     ix->profile.emplace_back("vocab_attempts", (float)vocab_attempts);
     ix->profile.emplace_back("lt_attempts", (float)rsp.lt_attempts);
     ix_guard.release();
@@ -4827,6 +4829,8 @@ vocab_again:  // (a docid term equal to a word term: the general path, from here
   ix->Vt = V;
   ix->profile = prof.finish();
   ix->profile.emplace_back("tok_attempts", (float)tok_attempts);
+  ix->profile.emplace_back("records_fast", (float)nF);
+  ix->profile.emplace_back("records_slow", (float)nslow);
   ix->profile.emplace_back("vocab_attempts", (float)vocab_attempts);
   ix->profile.emplace_back("lt_attempts", (float)rsp.lt_attempts);
   ix_guard.release();
