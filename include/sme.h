@@ -143,6 +143,9 @@ void sme_destroy(sme_ctx *ctx);
  *                   spelling suggestions cut their candidates by the same option
  *   "fuzzy_scan"    spelling suggestions: 0 (default) candidates from the trigram table, 1 every
  *                   word takes the whole vocabulary as candidates
+ *   "bool_chunk"    Boolean-query candidates per workgroup, 64..4096 in multiples of 64 (default 1024)
+ *   "bool_driver"   Boolean queries: 0 (default) the required group with the fewest postings
+ *                   supplies the candidates, 1 the first required group
  * Unknown names and out-of-range values are SME_EINVAL. */
 int sme_set_option(sme_ctx *ctx, const char *name, int64_t value);
 
@@ -359,6 +362,62 @@ int sme_index_suggest_terms_device(sme_index *ix, const uint8_t *words, const in
                                    int m, void *stream, const int64_t **d_sug_off, const int32_t **d_term_ids,
                                    const uint8_t **d_dist, int64_t *total);
 int sme_index_suggest_stats(const sme_index *ix, uint64_t *scanned_words, uint64_t *candidates);
+
+/* Boolean retrieval (no reference counterpart: rank() is one disjunctive sum over
+ * a flat term list).  A query is a list of groups, a group a list of term ids
+ * plus one flag: query i's groups are [q_offsets[i], q_offsets[i + 1]) (nq + 1
+ * entries from 0), group g's term slots term_ids[g_offsets[g] .. g_offsets[g + 1])
+ * (ngroups + 1 entries from 0, ngroups = q_offsets[nq]) and its flag g_flags[g];
+ * all host arrays.  A document matches a query when
+ *   - for every REQUIRED group (flag 0) it lies in at least one of the group's
+ *     posting lists: OR inside a group, AND across groups;
+ *   - for every EXCLUDED group (flag 1) it lies in none of them.
+ * Term id -1 is an unknown term, an empty list, as in sme_query_topk; an id
+ * outside [-1, V) is SME_EINVAL (the message names the query).  A required group
+ * without a posting therefore matches nothing, and so does a query without a
+ * required group -- the empty query, or exclusions only: pure negation is not
+ * offered.  A term in both a required and an excluded group contributes nothing
+ * to the result.  For K >= 2 the ids are k-gram ids.
+ * The score of a matching document is the fp64 sum, starting from 0.0, of its
+ * weight (sme_index_device_arrays' d_weight at the document's posting) over
+ * every term slot of every required group in listed order -- groups in order,
+ * slots in order within a group; a slot whose list does not hold the document
+ * adds nothing, a term listed twice counts twice, excluded slots add nothing.
+ * That is the sum rank() forms for the flat list of the required slots, so the
+ * score has the bits sme_query_topk gives the same document for that list.  The
+ * weights are read at call time (a call after sme_index_reweight uses the new
+ * ones).  order 0: a query's results by docno ascending (signed int32 order, as
+ * the postings are kept); order 1: by score descending, then docno ascending;
+ * both then cut to the first m entries (m == 0: no cut).  Query i's results are
+ * docno[] / score[] at [res_off[i], res_off[i + 1]); nq + 1 offsets, owned by the
+ * index until the next Boolean call on it (host memory from the host entry;
+ * device memory from the device entry, with *total = res_off[nq], total may be
+ * NULL).  A Boolean call leaves the buffers of the last wildcard expansion and
+ * suggestion call alone, and the other way round.  nq == 0 is valid.
+ * Limits: more than 64 groups or more than 1024 term slots in a query are
+ * SME_ELIMIT (the message names the query), as are 2^31 or more term slots in
+ * a batch and 2^31 or more matches in a batch BEFORE the cut.  q_offsets and
+ * g_offsets are never NULL when nq > 0; g_flags and term_ids may be NULL only
+ * in a batch without a group (q_offsets[nq] == 0) -- a NULL array otherwise is
+ * SME_EINVAL, also when every group of the batch is empty.  m < 0, an order other than 0 / 1, offsets that do not
+ * ascend from 0 or do not agree with each other, and a flag other than 0 / 1
+ * are SME_EINVAL.  An index without a query side (a chargram output, a
+ * records-only merged index) is SME_EINVAL, as the query entry points refuse.
+ * Candidates come from one required group, the driver: the one with the fewest
+ * postings, ties to the first ("bool_driver" 1: the first required group); every
+ * candidate is tested against all other groups by binary searches, so the
+ * driver never changes a result.  sme_query_boolean_stats reports on the last
+ * Boolean call on the index: the driver postings examined over all queries that
+ * could match (a query that matches nothing by the rules above adds none), and
+ * the matches before the cut. */
+int sme_query_boolean(sme_index *ix, const int32_t *term_ids, const int64_t *g_offsets, const uint8_t *g_flags,
+                      const int64_t *q_offsets, int nq, int order, int m, const int64_t **res_off,
+                      const int32_t **docno, const double **score);
+int sme_query_boolean_device(sme_index *ix, const int32_t *term_ids, const int64_t *g_offsets,
+                             const uint8_t *g_flags, const int64_t *q_offsets, int nq, int order, int m, void *stream,
+                             const int64_t **d_res_off, const int32_t **d_docno, const double **d_score,
+                             int64_t *total);
+int sme_query_boolean_stats(const sme_index *ix, uint64_t *candidates, uint64_t *matches);
 
 /* Batched rank(): query q has term ids term_ids[q_offsets[q] .. q_offsets[q+1])
  * in query-token order (duplicates count twice, -1 entries are skipped; an id

@@ -55,6 +55,7 @@ EXPORTS = [
     "sme_index_prepare_wildcards", "sme_index_wildcard_stats", "sme_index_expand_wildcards",
     "sme_index_expand_wildcards_device",
     "sme_index_suggest_terms", "sme_index_suggest_terms_device", "sme_index_suggest_stats",
+    "sme_query_boolean", "sme_query_boolean_device", "sme_query_boolean_stats",
 ]
 
 
@@ -139,6 +140,12 @@ def lib():
     L.sme_index_suggest_terms_device.argtypes = [vp, C.c_char_p, i64p, C.c_int, C.c_int, C.c_int, vp, C.POINTER(vp),
                                                  C.POINTER(vp), C.POINTER(vp), i64p]
     L.sme_index_suggest_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    f64p = C.POINTER(C.c_double)
+    L.sme_query_boolean.argtypes = [vp, i32p, i64p, u8p, i64p, C.c_int, C.c_int, C.c_int, C.POINTER(i64p),
+                                    C.POINTER(i32p), C.POINTER(f64p)]
+    L.sme_query_boolean_device.argtypes = [vp, i32p, i64p, u8p, i64p, C.c_int, C.c_int, C.c_int, vp, C.POINTER(vp),
+                                           C.POINTER(vp), C.POINTER(vp), i64p]
+    L.sme_query_boolean_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     _lib = L
     return L
 
@@ -577,6 +584,71 @@ class Index:
         _check(lib().sme_index_suggest_stats(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
 
+    @staticmethod
+    def boolean_arrays(queries):
+        """The C-ABI's three-level structure of a list of queries, each a list of
+        (term_ids, excluded) groups: (term_ids int32, g_offsets int64[ngroups+1],
+        g_flags uint8[ngroups], q_offsets int64[nq+1])."""
+        terms, goff, flags, qoff = [], [0], [], [0]
+        for groups in queries:
+            for ids, excluded in groups:
+                terms.extend(int(t) for t in ids)
+                goff.append(len(terms))
+                flags.append(int(excluded))
+            qoff.append(len(flags))
+        return (np.array(terms, np.int32), np.array(goff, np.int64), np.array(flags, np.uint8),
+                np.array(qoff, np.int64))
+
+    @staticmethod
+    def _boolean_ptrs(term_ids, g_offsets, g_flags, q_offsets):
+        # (an empty numpy array may hand out any pointer: keep one element behind each)
+        arrs = []
+        for a, dt in ((term_ids, np.int32), (g_offsets, np.int64), (g_flags, np.uint8), (q_offsets, np.int64)):
+            a = np.ascontiguousarray(a, dtype=dt)
+            arrs.append(a if a.size else np.zeros(1, dt))
+        t, g, f, q = arrs
+        return arrs, (t.ctypes.data_as(C.POINTER(C.c_int32)), g.ctypes.data_as(C.POINTER(C.c_int64)),
+                      f.ctypes.data_as(C.POINTER(C.c_uint8)), q.ctypes.data_as(C.POINTER(C.c_int64)))
+
+    def query_boolean(self, queries, order=0, m=0, arrays=None):
+        """sme_query_boolean: queries = a list of queries, each a list of
+        (term_ids, excluded) groups -- a document matches when it lies in at least
+        one posting list of every required group and in none of an excluded one;
+        term id -1 is an empty list.  Returns (res_off int64[nq+1], docno int32,
+        score float64): query i's matches are [res_off[i], res_off[i+1]), the
+        score the fp64 sum of the weights over the required slots in listed order,
+        ordered by docno ascending (order 0) or score descending then docno
+        ascending (order 1) and cut to the first m (0: no cut) (include/sme.h).
+        arrays: the structure as boolean_arrays returns it, instead of queries."""
+        t, g, f, q = arrays if arrays is not None else Index.boolean_arrays(queries)
+        nq = len(q) - 1
+        keep, ptrs = Index._boolean_ptrs(t, g, f, q)
+        ro, dn, sc = C.POINTER(C.c_int64)(), C.POINTER(C.c_int32)(), C.POINTER(C.c_double)()
+        _check(lib().sme_query_boolean(self._h, *ptrs, nq, int(order), int(m), C.byref(ro), C.byref(dn), C.byref(sc)))
+        off = np.ctypeslib.as_array(ro, (nq + 1,)).copy()
+        total = int(off[nq])
+        docno = np.ctypeslib.as_array(dn, (total,)).copy() if total else np.zeros(0, np.int32)
+        score = np.ctypeslib.as_array(sc, (total,)).copy() if total else np.zeros(0, np.float64)
+        return off, docno, score
+
+    def query_boolean_device(self, queries, order=0, m=0, stream=None, arrays=None):
+        """sme_query_boolean_device: (device pointer of res_off int64[nq+1], of
+        docno int32[total], of score float64[total], total); the arrays belong to
+        the index until its next Boolean call."""
+        t, g, f, q = arrays if arrays is not None else Index.boolean_arrays(queries)
+        keep, ptrs = Index._boolean_ptrs(t, g, f, q)
+        ro, dn, sc, tot = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int64()
+        _check(lib().sme_query_boolean_device(self._h, *ptrs, len(q) - 1, int(order), int(m), C.c_void_p(stream or 0),
+                                              C.byref(ro), C.byref(dn), C.byref(sc), C.byref(tot)))
+        return ro.value or 0, dn.value or 0, sc.value or 0, tot.value
+
+    def boolean_stats(self):
+        """(candidates, matches) of the last Boolean call: the driver postings
+        examined, and the matches before the cut."""
+        a, b = C.c_uint64(), C.c_uint64()
+        _check(lib().sme_query_boolean_stats(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
     def reweight(self, n_global, d_df_global=None, stream=None):
         """TF-IDF weights with all-reduced N (and df) of a doc-sharded index."""
         _check(lib().sme_index_reweight(self._h, n_global, C.c_void_p(d_df_global or 0), C.c_void_p(stream or 0)))
@@ -783,6 +855,39 @@ class IntDocVectorsForwardIndex:
                     made.append((toks[i], self.index.term(ids[i])))
         self._terms = [t for t in ids if t >= 0]
         return made
+
+    def get_boolean(self, words):
+        """A Boolean query from whitespace-separated words: every word is one
+        group, excluded if it starts with '-'.  A word holding '*' or '?' is
+        lower-cased and expanded (Index.expand_wildcards) into one OR-group; any
+        other word goes through processContent and each resulting token is a
+        group of its own -- a word that yields no token (a stopword) is dropped,
+        an unknown token is a group holding -1, so a required unknown word gives
+        no results.  Sets the groups for rank_boolean() and returns them, a list
+        of (term_ids, excluded).  A query holds at most 1024 term ids over all
+        its groups and at most 64 groups (include/sme.h): a wildcard word whose
+        expansion, with the other words' terms, passes that is not cut short --
+        rank_boolean() then raises the SmeError (SME_ELIMIT) query_boolean
+        raises, as rank() does after get_wildcard."""
+        groups = []
+        for w in words:
+            excluded = w.startswith("-")
+            if excluded:
+                w = w[1:]
+            if "*" in w or "?" in w:
+                _, ids = self.index.expand_wildcards([w.lower()])
+                groups.append(([int(t) for t in ids], excluded))
+            else:
+                toks = self.index.ctx.process_content(w)
+                if toks:
+                    groups.extend(([int(t)], excluded) for t in self.index.lookup(toks))
+        self._groups = groups
+        return groups
+
+    def rank_boolean(self, k=10):
+        """The first k documents (score desc, docno asc) matching get_boolean's groups."""
+        _, dn, _ = self.index.query_boolean([getattr(self, "_groups", [])], order=1, m=k)
+        return [int(d) for d in dn]
 
     def rank(self, k=10):
         if not self._terms:

@@ -346,6 +346,13 @@ int sme_set_option(sme_ctx *cx, const char *name, int64_t v) {
     } else if (n == "fuzzy_scan") {
       range(0, 1);
       cx->opt_fuzzy_scan = v;
+    } else if (n == "bool_chunk") {
+      range(64, 4096);
+      if (v % 64) throw sme::Error(SME_EINVAL, "option " + n + " must be a multiple of 64");
+      cx->opt_bool_chunk = v;
+    } else if (n == "bool_driver") {
+      range(0, 1);
+      cx->opt_bool_driver = v;
     } else {
       throw sme::Error(SME_EINVAL, "unknown option " + n);
     }
@@ -831,6 +838,73 @@ int sme_index_suggest_stats(const sme_index *ix, uint64_t *scanned_words, uint64
     if (!ix || !scanned_words || !candidates) throw sme::Error(SME_EINVAL, "null argument");
     *scanned_words = ix->fz_scanned;
     *candidates = ix->fz_cands;
+  });
+}
+
+// Boolean retrieval runs over the query side of a TermKGramDocIndexer index
+static void need_boolean_args(const sme_index *ix, const int32_t *term_ids, const int64_t *g_offsets,
+                              const uint8_t *g_flags, const int64_t *q_offsets, int nq, int order, int m) {
+  if (!ix || nq < 0 || (nq > 0 && !q_offsets)) throw sme::Error(SME_EINVAL, "bad argument");
+  if (ix->job != 0) throw sme::Error(SME_EINVAL, "boolean: not a TermKGramDocIndexer index");
+  need_query_side(ix);
+  if (m < 0) throw sme::Error(SME_EINVAL, "boolean: m must be >= 0");
+  if (order != 0 && order != 1) throw sme::Error(SME_EINVAL, "boolean: order must be 0 (docno) or 1 (score)");
+  // g_offsets always holds an entry; only a batch without a group may leave
+  // g_flags and term_ids NULL (sme::query_boolean validates the offsets
+  // themselves before anything is read through them)
+  if (nq > 0 && (!g_offsets || (q_offsets[nq] != 0 && (!g_flags || !term_ids))))
+    throw sme::Error(SME_EINVAL, "bad argument");
+}
+
+int sme_query_boolean_device(sme_index *ix, const int32_t *term_ids, const int64_t *g_offsets, const uint8_t *g_flags,
+                             const int64_t *q_offsets, int nq, int order, int m, void *stream,
+                             const int64_t **d_res_off, const int32_t **d_docno, const double **d_score,
+                             int64_t *total) {
+  return guard([&] {
+    if (!d_res_off || !d_docno || !d_score) throw sme::Error(SME_EINVAL, "null argument");
+    need_boolean_args(ix, term_ids, g_offsets, g_flags, q_offsets, nq, order, m);
+    set_device(ix->ctx);
+    sme::query_boolean(ix, term_ids, g_offsets, g_flags, q_offsets, nq, order, m, stream_of(ix->ctx, stream));
+    *d_res_off = (const int64_t *)ix->d_bq_off.p;
+    *d_docno = (const int32_t *)ix->d_bq_docno.p;
+    *d_score = (const double *)ix->d_bq_score.p;
+    if (total) *total = ix->bq_total;
+  });
+}
+
+int sme_query_boolean(sme_index *ix, const int32_t *term_ids, const int64_t *g_offsets, const uint8_t *g_flags,
+                      const int64_t *q_offsets, int nq, int order, int m, const int64_t **res_off,
+                      const int32_t **docno, const double **score) {
+  return guard([&] {
+    if (!res_off || !docno || !score) throw sme::Error(SME_EINVAL, "null argument");
+    need_boolean_args(ix, term_ids, g_offsets, g_flags, q_offsets, nq, order, m);
+    set_device(ix->ctx);
+    hipStream_t st = ix->ctx->own_stream;
+    sme::query_boolean(ix, term_ids, g_offsets, g_flags, q_offsets, nq, order, m, st);
+    const size_t tot = (size_t)ix->bq_total;
+    ix->h_bq_off.resize((size_t)nq + 1);
+    ix->h_bq_docno.resize(tot + 1);  // (never an empty vector: data() stays a valid pointer)
+    ix->h_bq_score.resize(tot + 1);
+    SME_HIP(hipMemcpyAsync(ix->h_bq_off.data(), ix->d_bq_off.p, ((size_t)nq + 1) * sizeof(int64_t),
+                           hipMemcpyDeviceToHost, st));
+    if (tot) {
+      SME_HIP(hipMemcpyAsync(ix->h_bq_docno.data(), ix->d_bq_docno.p, tot * sizeof(int32_t), hipMemcpyDeviceToHost,
+                             st));
+      SME_HIP(hipMemcpyAsync(ix->h_bq_score.data(), ix->d_bq_score.p, tot * sizeof(double), hipMemcpyDeviceToHost,
+                             st));
+    }
+    SME_HIP(hipStreamSynchronize(st));
+    *res_off = ix->h_bq_off.data();
+    *docno = ix->h_bq_docno.data();
+    *score = ix->h_bq_score.data();
+  });
+}
+
+int sme_query_boolean_stats(const sme_index *ix, uint64_t *candidates, uint64_t *matches) {
+  return guard([&] {
+    if (!ix || !candidates || !matches) throw sme::Error(SME_EINVAL, "null argument");
+    *candidates = ix->bq_cands;
+    *matches = ix->bq_matches;
   });
 }
 

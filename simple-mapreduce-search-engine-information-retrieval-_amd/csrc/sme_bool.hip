@@ -1,0 +1,433 @@
+// sme_bool.hip -- Boolean retrieval: a batch of queries, each a list of groups of
+// term ids (a required group: the document lies in at least one of its posting
+// lists; an excluded group: in none) -> per query the matching documents with
+// their TF-IDF scores, ordered by docno or by score and cut to the first m, over
+// the query-side CSR (d_off / d_docno_d / d_w).
+//
+// k_bool_plan picks per query the driver, the required group with the fewest
+// postings (or the first one), whose slots' posting lists are the candidates; the
+// candidate ranges are cut into chunks, and k_bool_chunks -- once counting, once
+// emitting -- tests every candidate against the query's other lists by binary
+// searches bounded to the chunk's docno range, one workgroup per chunk, one
+// candidate per thread, and sums a survivor's weights in listed slot order.
+// Stable sorts over an index permutation (docno, then the score key, then the
+// query) and a gather order and cut the matches.  Every candidate is tested
+// against every group, so the driver never changes a result.
+#include <hip/hip_runtime.h>
+#include <string.h>
+
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include "sme_bool.hpp"
+#include "sme_internal.hpp"
+
+namespace sme {
+namespace {
+constexpr int kNT = 256;  // threads of the chunk kernels
+constexpr int64_t kMaxGrid = 1 << 20;
+
+unsigned grid_for(int64_t n) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + kNT - 1) / kNT, 65536)); }
+
+struct Batch {           // the uploaded batch (device pointers into one block)
+  const int64_t *goff;   // [ngroups + 1] slot offsets
+  const int64_t *qoff;   // [nq + 1] group offsets
+  const int32_t *term;   // [nt] term id per slot (-1: no postings)
+  const uint8_t *gflag;  // [ngroups] 0 required, 1 excluded
+};
+
+// One thread per query.  Per slot s: its posting list docno[sbeg .. sbeg + scnt)
+// and its query sq; per query the driver group qdrv (-1: the query matches
+// nothing -- no required group, or a required group without a posting); nchunk[s]
+// = chunks of slot s as a candidate range (driver slots only; entry nt = 0).
+// *cands += the driver's postings.
+__global__ void k_bool_plan(Batch b, int nq, int64_t nt, const int64_t *__restrict__ doff, int chunk, int first_driver,
+                            int64_t *__restrict__ sbeg, int32_t *__restrict__ scnt, int32_t *__restrict__ sq,
+                            int32_t *__restrict__ qdrv, int64_t *__restrict__ nchunk,
+                            unsigned long long *__restrict__ cands) {
+  // (64-bit counters: nq + the grid's stride may pass INT_MAX)
+  for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q <= nq; q += (int64_t)gridDim.x * blockDim.x) {
+    if (q == nq) {
+      nchunk[nt] = 0;
+      continue;
+    }
+    const int64_t g0 = b.qoff[q], g1 = b.qoff[q + 1];
+    int64_t drv = -1, best = 0;
+    bool dead = false;
+    for (int64_t g = g0; g < g1; g++) {
+      int64_t sum = 0;
+      for (int64_t s = b.goff[g]; s < b.goff[g + 1]; s++) {
+        const int32_t t = b.term[s];
+        const int64_t beg = t < 0 ? 0 : doff[t];
+        const int64_t cnt = t < 0 ? 0 : doff[t + 1] - beg;
+        sbeg[s] = beg;
+        scnt[s] = (int32_t)cnt;
+        sq[s] = (int32_t)q;
+        sum += cnt;
+      }
+      if (b.gflag[g] != 0) continue;
+      dead |= sum == 0;
+      if (drv < 0 || (!first_driver && sum < best)) {
+        drv = g;
+        best = sum;
+      }
+    }
+    if (dead) drv = -1;
+    qdrv[q] = (int32_t)(drv < 0 ? -1 : drv - g0);
+    const int64_t d0 = drv < 0 ? 0 : b.goff[drv], d1 = drv < 0 ? 0 : b.goff[drv + 1];
+    for (int64_t s = b.goff[g0]; s < b.goff[g1]; s++)
+      nchunk[s] = s >= d0 && s < d1 ? ((int64_t)scnt[s] + chunk - 1) / chunk : 0;
+    if (drv >= 0) atomicAdd(cands, (unsigned long long)best);
+  }
+}
+
+// The chunk's range: the last one whose first chunk is at or before `ch` (ranges
+// without candidates own no chunk).
+__device__ __forceinline__ int64_t chunk_range(const int64_t *__restrict__ choff, int64_t R, int64_t ch) {
+  int64_t lo = 0, hi = R;  // first range with choff > ch
+  while (lo < hi) {
+    const int64_t m = (lo + hi) >> 1;
+    if (choff[m] <= ch)
+      lo = m + 1;
+    else
+      hi = m;
+  }
+  return lo - 1;
+}
+
+// first index of the ascending p[0 .. n) with p[i] >= d (UPPER: p[i] > d)
+template <bool UPPER>
+__device__ __forceinline__ int bound(const int32_t *__restrict__ p, int n, int32_t d) {
+  int lo = 0, hi = n;
+  while (lo < hi) {
+    const int m = (lo + hi) >> 1;
+    if (UPPER ? p[m] <= d : p[m] < d)
+      lo = m + 1;
+    else
+      hi = m;
+  }
+  return lo;
+}
+// the posting of document d in docno[start .. start + n), or -1
+__device__ __forceinline__ int64_t find_doc(const int32_t *__restrict__ docno, int64_t start, int n, int32_t d) {
+  const int at = bound<false>(docno + start, n, d);
+  return at < n && docno[start + at] == d ? start + at : -1;
+}
+
+// One workgroup per chunk (grid-stride over the chunks) of at most `chunk`
+// consecutive postings of one driver slot.  The chunk's docnos lie in [first,
+// last]; per slot of the query the sub-range of its list that can hold such a
+// docno (two bounds) is staged in LDS, with the groups' slot ranges and flags.
+// A required group other than the driver whose sub-ranges are all empty rejects
+// the whole chunk.  Then the candidates are taken kNT at a time, one per thread:
+// every other required group must hold it (OR over the group's slots), no
+// excluded slot may, and one an earlier slot of the driver group also holds is
+// dropped, so a document is emitted once per query.
+// EMIT = false: mcnt[ch] = matches of the chunk.  EMIT = true: at moff[ch] + rank
+// (rank from the waves' ballots) the match's docno, query and score -- the sum
+// from 0.0 of w at its posting over the required slots in listed order.
+template <bool EMIT>
+__global__ __launch_bounds__(kNT) void k_bool_chunks(Batch b, int64_t R, const int64_t *__restrict__ choff, int64_t NC,
+                                                     const int64_t *__restrict__ sbeg,
+                                                     const int32_t *__restrict__ scnt, const int32_t *__restrict__ sq,
+                                                     const int32_t *__restrict__ qdrv,
+                                                     const int32_t *__restrict__ docno, const double *__restrict__ w,
+                                                     int chunk, int64_t *__restrict__ mcnt,
+                                                     const int64_t *__restrict__ moff, int32_t *__restrict__ mdoc,
+                                                     double *__restrict__ mscore, uint32_t *__restrict__ mq) {
+  __shared__ int64_t s_start[boolq::kMaxSlots];
+  __shared__ int32_t s_len[boolq::kMaxSlots];
+  __shared__ int32_t s_gbeg[boolq::kMaxGroups + 1];
+  __shared__ uint8_t s_gflag[boolq::kMaxGroups];
+  __shared__ int s_wsum[kNT / 64];
+  __shared__ int s_reject;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  for (int64_t ch = blockIdx.x; ch < NC; ch += gridDim.x) {
+    const int64_t r = chunk_range(choff, R, ch);  // the driver slot
+    const int q = sq[r];
+    const int64_t g0 = b.qoff[q];
+    const int ng = (int)(b.qoff[q + 1] - g0);  // <= kMaxGroups (validated on the host)
+    const int64_t s0 = b.goff[g0];
+    const int S = (int)(b.goff[g0 + ng] - s0);  // <= kMaxSlots
+    const int dg = qdrv[q], ds = (int)(r - s0);
+    const int64_t c0 = (ch - choff[r]) * chunk;
+    const int len = (int)min((int64_t)chunk, (int64_t)scnt[r] - c0);  // >= 1
+    const int64_t base = sbeg[r] + c0;
+    const int32_t first = docno[base], last = docno[base + len - 1];
+    if (tid <= ng) s_gbeg[tid] = (int32_t)(b.goff[g0 + tid] - s0);
+    if (tid < ng) s_gflag[tid] = b.gflag[g0 + tid];
+    if (tid == 0) s_reject = 0;
+    for (int j = tid; j < S; j += kNT) {
+      const int64_t beg = sbeg[s0 + j];
+      const int n = scnt[s0 + j];
+      const int lo = bound<false>(docno + beg, n, first);
+      const int hi = lo + bound<true>(docno + beg + lo, n - lo, last);
+      s_start[j] = beg + lo;
+      s_len[j] = hi - lo;
+    }
+    __syncthreads();
+    if (tid < ng && tid != dg && s_gflag[tid] == 0) {
+      int any = 0;
+      for (int j = s_gbeg[tid]; j < s_gbeg[tid + 1]; j++) any |= s_len[j];
+      if (any == 0) s_reject = 1;
+    }
+    __syncthreads();
+    const bool reject = s_reject != 0;
+    int64_t run = EMIT ? moff[ch] : 0;  // matches of the rounds before
+    for (int rd = 0; !reject && rd < len; rd += kNT) {
+      const int c = rd + tid;
+      bool hit = false;
+      int32_t d = 0;
+      if (c < len) {
+        d = docno[base + c];
+        hit = true;
+        for (int g = 0; hit && g < ng; g++) {
+          if (g == dg || s_gflag[g] != 0) continue;
+          bool held = false;
+          for (int j = s_gbeg[g]; !held && j < s_gbeg[g + 1]; j++) held = find_doc(docno, s_start[j], s_len[j], d) >= 0;
+          hit = held;
+        }
+        for (int g = 0; hit && g < ng; g++) {
+          if (s_gflag[g] == 0) continue;
+          for (int j = s_gbeg[g]; hit && j < s_gbeg[g + 1]; j++) hit = find_doc(docno, s_start[j], s_len[j], d) < 0;
+        }
+        for (int j = s_gbeg[dg]; hit && j < ds; j++) hit = find_doc(docno, s_start[j], s_len[j], d) < 0;
+      }
+      const unsigned long long m = __ballot(hit);
+      if (lane == 0) s_wsum[wv] = __popcll(m);
+      __syncthreads();
+      int before = 0, total = 0;
+#pragma unroll
+      for (int i = 0; i < kNT / 64; i++) {
+        const int s = s_wsum[i];
+        before += i < wv ? s : 0;
+        total += s;
+      }
+      if (EMIT && hit) {
+        double sc = 0.0;
+        for (int g = 0; g < ng; g++) {
+          if (s_gflag[g] != 0) continue;
+          for (int j = s_gbeg[g]; j < s_gbeg[g + 1]; j++) {
+            const int64_t at = find_doc(docno, s_start[j], s_len[j], d);
+            if (at >= 0) sc += w[at];
+          }
+        }
+        const int64_t at = run + before + __popcll(m & ((1ull << lane) - 1));
+        mdoc[at] = d;
+        mscore[at] = sc;
+        mq[at] = (uint32_t)q;
+      }
+      run += total;
+      __syncthreads();  // s_wsum is rewritten
+    }
+    if (!EMIT && tid == 0) mcnt[ch] = run;
+    __syncthreads();  // the staged query is rewritten
+  }
+}
+
+// woff[i] = matches before query i's first chunk (i = n: all of them); a query's
+// first range is its first slot, and a query without slots has the next one's
+__global__ void k_bool_offs(Batch b, const int64_t *__restrict__ choff, const int64_t *__restrict__ moff, int n,
+                            int64_t *__restrict__ woff) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i <= n; i += (int64_t)gridDim.x * blockDim.x)
+    woff[i] = moff[choff[b.goff[b.qoff[i]]]];
+}
+// kept[i] = query i's matches after the cut (m = 0: no cut); kept[n] = 0
+__global__ void k_bool_cut(const int64_t *__restrict__ woff, int n, int64_t m, int64_t *__restrict__ kept) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i <= n; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t c = i < n ? woff[i + 1] - woff[i] : 0;
+    kept[i] = m > 0 && c > m ? m : c;
+  }
+}
+// sort keys of the matches: the docno key and the identity permutation ...
+__global__ void k_bool_key_docno(const int32_t *__restrict__ mdoc, int64_t n, uint32_t *__restrict__ key,
+                                 uint32_t *__restrict__ perm) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    key[i] = boolq::docno_key(mdoc[i]);
+    perm[i] = (uint32_t)i;
+  }
+}
+// ... and, through the permutation so far, the score key and the query
+__global__ void k_bool_key_score(const double *__restrict__ mscore, const uint32_t *__restrict__ perm, int64_t n,
+                                 uint64_t *__restrict__ key) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+    key[i] = boolq::score_key(mscore[perm[i]]);
+}
+__global__ void k_bool_key_query(const uint32_t *__restrict__ mq, const uint32_t *__restrict__ perm, int64_t n,
+                                 uint32_t *__restrict__ key) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+    key[i] = mq[perm[i]];
+}
+// Sorted match x (query qs[x], match perm[x]) is the (x - woff[q])-th of its
+// query: kept if that is below the cut.
+__global__ void k_bool_gather(const uint32_t *__restrict__ qs, const uint32_t *__restrict__ perm,
+                              const int32_t *__restrict__ mdoc, const double *__restrict__ mscore, int64_t total,
+                              const int64_t *__restrict__ woff, const int64_t *__restrict__ roff, int64_t m,
+                              int32_t *__restrict__ out_docno, double *__restrict__ out_score) {
+  for (int64_t x = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; x < total; x += (int64_t)gridDim.x * blockDim.x) {
+    const uint32_t q = qs[x];
+    const int64_t rk = x - woff[q];
+    if (m > 0 && rk >= m) continue;
+    const uint32_t i = perm[x];
+    out_docno[roff[q] + rk] = mdoc[i];
+    out_score[roff[q] + rk] = mscore[i];
+  }
+}
+
+// appends an aligned section of `count` T to the upload blob; *at = its byte offset
+template <typename T>
+void section(std::vector<uint8_t> &blob, size_t count, size_t *at) {
+  const size_t a = (blob.size() + alignof(T) - 1) / alignof(T) * alignof(T);
+  blob.resize(a + count * sizeof(T));
+  *at = a;
+}
+}  // namespace
+
+void query_boolean(sme_index *ix, const int32_t *term_ids, const int64_t *g_offsets, const uint8_t *g_flags,
+                   const int64_t *q_offsets, int nq, int order, int m, hipStream_t st) {
+  sme_ctx *cx = ix->ctx;
+  int bad = -1;
+  const int rc = boolq::validate(term_ids, -1, g_offsets, -1, g_flags, q_offsets, nq, ix->V, &bad);
+  const std::string where = bad >= 0 ? "query " + std::to_string(bad) + ": " : std::string();
+  switch (rc) {
+    case boolq::B_OK:
+      break;
+    case boolq::B_OFFSETS:
+      throw Error(SME_EINVAL, "boolean " + where + "offsets not ascending from 0 or inconsistent");
+    case boolq::B_FLAG:
+      throw Error(SME_EINVAL, "boolean " + where + "a group flag other than 0 (required) or 1 (excluded)");
+    case boolq::B_GROUPS:
+      throw Error(SME_ELIMIT, "boolean " + where + "more than 64 groups");
+    case boolq::B_SLOTS:
+      throw Error(SME_ELIMIT, "boolean " + where + "more than 1024 term slots");
+    default:
+      throw Error(SME_EINVAL, "boolean " + where + "a term id outside [-1, V)");
+  }
+  ix->bq_total = 0;
+  ix->bq_cands = 0;
+  ix->bq_matches = 0;
+  int64_t *d_roff = ix->d_bq_off.as<int64_t>((size_t)nq + 1);
+  if (nq == 0) {
+    SME_HIP(hipMemsetAsync(d_roff, 0, sizeof(int64_t), st));
+    SME_HIP(hipStreamSynchronize(st));
+    return;
+  }
+  const int64_t ng = q_offsets[nq], nt = g_offsets[ng];
+  if (nt >= (int64_t(1) << 31)) throw Error(SME_ELIMIT, "boolean batch: 2^31 or more term slots");
+  // one upload: slot offsets | group offsets | term ids | flags
+  std::vector<uint8_t> blob;
+  size_t a_goff, a_qoff, a_term, a_flag;
+  section<int64_t>(blob, (size_t)ng + 1, &a_goff);
+  section<int64_t>(blob, (size_t)nq + 1, &a_qoff);
+  section<int32_t>(blob, (size_t)nt, &a_term);
+  section<uint8_t>(blob, (size_t)ng, &a_flag);
+  memcpy(blob.data() + a_goff, g_offsets, ((size_t)ng + 1) * sizeof(int64_t));
+  memcpy(blob.data() + a_qoff, q_offsets, ((size_t)nq + 1) * sizeof(int64_t));
+  if (nt) memcpy(blob.data() + a_term, term_ids, (size_t)nt * sizeof(int32_t));
+  if (ng) memcpy(blob.data() + a_flag, g_flags, (size_t)ng);
+  const int chunk = (int)cx->opt_bool_chunk;
+  const int64_t R = nt;  // one candidate range per slot (driver slots own chunks)
+  // temporaries of this call: pooled blocks, back in the pool on return
+  DevBuf in, sbb, scb, sqb, qdb, chb, mob, cnd, wob, kpb, scn, mdb, msb, mqb, ka, kb, pa, pb, pc, sa, sb, radix;
+  for (DevBuf *b : {&in, &sbb, &scb, &sqb, &qdb, &chb, &mob, &cnd, &wob, &kpb, &scn, &mdb, &msb, &mqb, &ka, &kb, &pa, &pb,
+                    &pc, &sa, &sb, &radix})
+    b->pool = &cx->pool;
+  try {
+    const uint8_t *d_in = in.as<uint8_t>(blob.size());
+    SME_HIP(hipMemcpyAsync((void *)d_in, blob.data(), blob.size(), hipMemcpyHostToDevice, st));
+    const Batch b{(const int64_t *)(d_in + a_goff), (const int64_t *)(d_in + a_qoff), (const int32_t *)(d_in + a_term),
+                  (const uint8_t *)(d_in + a_flag)};
+    int64_t *sbeg = sbb.as<int64_t>((size_t)nt);
+    int32_t *scnt = scb.as<int32_t>((size_t)nt);
+    int32_t *sq = sqb.as<int32_t>((size_t)nt);
+    int32_t *qdrv = qdb.as<int32_t>((size_t)nq);
+    int64_t *choff = chb.as<int64_t>((size_t)R + 1);
+    unsigned long long *d_cands = cnd.as<unsigned long long>(1);
+    const int64_t *doff = (const int64_t *)ix->d_off.p;
+    const int32_t *docno = (const int32_t *)ix->d_docno_d.p;
+    const double *w = (const double *)ix->d_w.p;
+    SME_HIP(hipMemsetAsync(d_cands, 0, sizeof(unsigned long long), st));
+    hipLaunchKernelGGL(k_bool_plan, dim3(grid_for((int64_t)nq + 1)), dim3(kNT), 0, st, b, nq, nt, doff, chunk,
+                       (int)cx->opt_bool_driver, sbeg, scnt, sq, qdrv, choff, d_cands);
+    SME_CHECK_LAUNCH();
+    excl_scan<int64_t>(choff, choff, R + 1, scn, st);
+    int64_t NC = 0;
+    unsigned long long cands = 0;
+    SME_HIP(hipMemcpyAsync(&NC, choff + R, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    SME_HIP(hipMemcpyAsync(&cands, d_cands, sizeof(cands), hipMemcpyDeviceToHost, st));
+    SME_HIP(hipStreamSynchronize(st));
+    // matches per chunk, scanned in place (entry NC = all matches)
+    int64_t *moff = mob.as<int64_t>((size_t)NC + 1);
+    int64_t total = 0;
+    const unsigned cgrid = (unsigned)std::max<int64_t>(1, std::min(NC, kMaxGrid));
+    SME_HIP(hipMemsetAsync(moff + NC, 0, sizeof(int64_t), st));
+    if (NC > 0) {
+      hipLaunchKernelGGL(k_bool_chunks<false>, dim3(cgrid), dim3(kNT), 0, st, b, R, (const int64_t *)choff, NC,
+                         (const int64_t *)sbeg, (const int32_t *)scnt, (const int32_t *)sq, (const int32_t *)qdrv, docno,
+                         w, chunk, moff, (const int64_t *)nullptr, (int32_t *)nullptr, (double *)nullptr,
+                         (uint32_t *)nullptr);
+      SME_CHECK_LAUNCH();
+      excl_scan<int64_t>(moff, moff, NC + 1, scn, st);
+      SME_HIP(hipMemcpyAsync(&total, moff + NC, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+      SME_HIP(hipStreamSynchronize(st));
+    }
+    if (total >= (int64_t(1) << 31)) throw Error(SME_ELIMIT, "boolean: 2^31 or more matches in one batch");
+    int64_t *woff = wob.as<int64_t>((size_t)nq + 1);
+    int64_t *kept = kpb.as<int64_t>((size_t)nq + 1);
+    hipLaunchKernelGGL(k_bool_offs, dim3(grid_for((int64_t)nq + 1)), dim3(kNT), 0, st, b, (const int64_t *)choff,
+                       (const int64_t *)moff, nq, woff);
+    hipLaunchKernelGGL(k_bool_cut, dim3(grid_for((int64_t)nq + 1)), dim3(kNT), 0, st, (const int64_t *)woff, nq, (int64_t)m,
+                       kept);
+    SME_CHECK_LAUNCH();
+    excl_scan<int64_t>(kept, d_roff, (int64_t)nq + 1, scn, st);
+    int64_t out_total = 0;
+    SME_HIP(hipMemcpyAsync(&out_total, d_roff + nq, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    SME_HIP(hipStreamSynchronize(st));
+    int32_t *out_docno = ix->d_bq_docno.as<int32_t>((size_t)out_total);
+    double *out_score = ix->d_bq_score.as<double>((size_t)out_total);
+    if (total > 0) {
+      const size_t T = (size_t)total;
+      int32_t *mdoc = mdb.as<int32_t>(T);
+      double *mscore = msb.as<double>(T);
+      uint32_t *mq = mqb.as<uint32_t>(T);
+      uint32_t *k0 = ka.as<uint32_t>(T), *k1 = kb.as<uint32_t>(T);
+      uint32_t *p0 = pa.as<uint32_t>(T), *p1 = pb.as<uint32_t>(T);
+      hipLaunchKernelGGL(k_bool_chunks<true>, dim3(cgrid), dim3(kNT), 0, st, b, R, (const int64_t *)choff, NC,
+                         (const int64_t *)sbeg, (const int32_t *)scnt, (const int32_t *)sq, (const int32_t *)qdrv, docno,
+                         w, chunk, (int64_t *)nullptr, (const int64_t *)moff, mdoc, mscore, mq);
+      SME_CHECK_LAUNCH();
+      // least significant key first, every pass stable: docno, (score,) query
+      const unsigned g = grid_for(total);
+      hipLaunchKernelGGL(k_bool_key_docno, dim3(g), dim3(kNT), 0, st, (const int32_t *)mdoc, total, k0, p0);
+      sort_pairs<uint32_t>(k0, k1, p0, p1, total, 32, radix, st);
+      uint32_t *perm = p1, *spare = p0;
+      if (order == 1) {
+        uint64_t *s0 = sa.as<uint64_t>(T), *s1 = sb.as<uint64_t>(T);
+        hipLaunchKernelGGL(k_bool_key_score, dim3(g), dim3(kNT), 0, st, (const double *)mscore,
+                           (const uint32_t *)perm, total, s0);
+        uint32_t *p2 = pc.as<uint32_t>(T);
+        sort_pairs<uint64_t>(s0, s1, perm, p2, total, 64, radix, st);
+        perm = p2;
+      }
+      hipLaunchKernelGGL(k_bool_key_query, dim3(g), dim3(kNT), 0, st, (const uint32_t *)mq, (const uint32_t *)perm,
+                         total, k0);
+      int qbits = 1;
+      while (qbits < 32 && (int64_t(1) << qbits) < nq) qbits++;
+      sort_pairs<uint32_t>(k0, k1, perm, spare, total, qbits, radix, st);
+      hipLaunchKernelGGL(k_bool_gather, dim3(g), dim3(kNT), 0, st, (const uint32_t *)k1, (const uint32_t *)spare,
+                         (const int32_t *)mdoc, (const double *)mscore, total, (const int64_t *)woff,
+                         (const int64_t *)d_roff, (int64_t)m, out_docno, out_score);
+      SME_CHECK_LAUNCH();
+    }
+    SME_HIP(hipStreamSynchronize(st));
+    ix->bq_total = out_total;
+    ix->bq_cands = (uint64_t)cands;
+    ix->bq_matches = (uint64_t)total;
+  } catch (...) {
+    (void)hipStreamSynchronize(st);  // the upload may still read `blob`, kernels the temporaries
+    throw;
+  }
+}
+
+}  // namespace sme

@@ -69,6 +69,8 @@ struct sme_ctx {
   int64_t opt_wild_scan = 0;      // "wild_scan": 1 = every wildcard pattern takes the whole vocabulary as candidates
   int64_t opt_wild_chunk = 1024;  // "wild_chunk": wildcard candidates per workgroup (64..4096, multiples of 64)
   int64_t opt_fuzzy_scan = 0;      // "fuzzy_scan": 1 = every suggestion word takes the whole vocabulary as candidates
+  int64_t opt_bool_chunk = 1024;  // "bool_chunk": Boolean-query candidates per workgroup (64..4096, multiples of 64)
+  int64_t opt_bool_driver = 0;    // "bool_driver": 0 = the required group with the fewest postings drives, 1 = the first
   int64_t opt_corpus_keep = int64_t(16) << 30;  // "corpus_keep_bytes": host-corpus builds keep their device copy
                                                 // (no hipMalloc next build) only up to this size
   // pinned host staging of device -> host record copies into pageable caller
@@ -173,6 +175,17 @@ struct sme_index {
   std::vector<int64_t> h_fz_off;
   std::vector<int32_t> h_fz_ids;
   std::vector<uint8_t> h_fz_dist;
+  // Boolean retrieval (sme_bool.hip): the last call's outputs (owned by the index
+  // until the next one; its temporaries are pooled blocks of the call) and what
+  // it counted
+  sme::DevBuf d_bq_off;    // int64 [nq + 1]  result offsets
+  sme::DevBuf d_bq_docno;  // int32 [total]   matching documents
+  sme::DevBuf d_bq_score;  // double [total]  their scores
+  int64_t bq_total = 0;
+  uint64_t bq_cands = 0, bq_matches = 0;  // driver postings examined; matches before the cut
+  std::vector<int64_t> h_bq_off;
+  std::vector<int32_t> h_bq_docno;
+  std::vector<double> h_bq_score;
   // stage timings of the build that produced this index (ms)
   std::vector<std::pair<std::string, float>> profile;
   ~sme_index() { ctx->live_indexes--; }  // members (pooled buffers) are released after this body
@@ -181,7 +194,7 @@ struct sme_index {
     for (sme::DevBuf *b : {&d_term_off, &d_term_chars, &d_off, &d_docno_d, &d_tf_d, &d_w, &d_idf, &d_lut, &d_gram, &d_docno_o,
                            &d_tf_o, &d_rec_docno, &d_rec_first, &d_ser, &d_hrow_of, &d_heavy, &d_spk, &d_wkeys, &d_wgoff,
                            &d_wgterm, &d_wx_off, &d_wx_ids, &d_wx_in, &d_wx_plan, &d_wx_choff, &d_wx_moff, &d_wx_scan, &d_fz_off,
-                           &d_fz_ids, &d_fz_dist})
+                           &d_fz_ids, &d_fz_dist, &d_bq_off, &d_bq_docno, &d_bq_score})
       b->pool = &c->pool;
   }
 };
@@ -334,4 +347,10 @@ void expand_wildcards(sme_index *ix, const uint8_t *patterns, const int64_t *off
 // d_fz_dist / fz_total, and the call's counts fz_scanned / fz_cands
 void suggest_terms(sme_index *ix, const uint8_t *words, const int64_t *offs, int n, int max_dist, int m,
                    hipStream_t st);
+// Boolean retrieval (sme_bool.hip): nq queries of required / excluded term groups
+// (host arrays, validated here) -> per query the matching documents and scores,
+// ordered (0 docno asc, 1 score desc then docno asc) and cut to m: ix->d_bq_off /
+// d_bq_docno / d_bq_score / bq_total, and the call's counts bq_cands / bq_matches
+void query_boolean(sme_index *ix, const int32_t *term_ids, const int64_t *g_offsets, const uint8_t *g_flags,
+                   const int64_t *q_offsets, int nq, int order, int m, hipStream_t st);
 }  // namespace sme
