@@ -6,10 +6,11 @@
 //
 // k_bool_plan picks per query the driver, the required group with the fewest
 // postings (or the first one), whose slots' posting lists are the candidates; the
-// candidate ranges are cut into chunks, and k_bool_chunks -- once counting, once
-// emitting -- tests every candidate against the query's other lists by binary
-// searches bounded to the chunk's docno range, one workgroup per chunk, one
-// candidate per thread, and sums a survivor's weights in listed slot order.
+// candidate ranges are cut into chunks, and the chunk filter of sme_chunks.hpp --
+// once counting, once emitting -- tests every candidate against the query's other
+// lists by binary searches bounded to the chunk's docno range (BoolOp), one
+// workgroup per chunk, one candidate per thread, and sums a survivor's weights in
+// listed slot order.
 // Stable sorts over an index permutation (docno, then the score key, then the
 // query) and a gather order and cut the matches.  Every candidate is tested
 // against every group, so the driver never changes a result.
@@ -21,14 +22,12 @@
 #include <vector>
 
 #include "sme_bool.hpp"
+#include "sme_chunks.hpp"
 #include "sme_internal.hpp"
 
 namespace sme {
 namespace {
-constexpr int kNT = 256;  // threads of the chunk kernels
-constexpr int64_t kMaxGrid = 1 << 20;
-
-unsigned grid_for(int64_t n) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + kNT - 1) / kNT, 65536)); }
+using namespace chunks;
 
 struct Batch {           // the uploaded batch (device pointers into one block)
   const int64_t *goff;   // [ngroups + 1] slot offsets
@@ -82,164 +81,112 @@ __global__ void k_bool_plan(Batch b, int nq, int64_t nt, const int64_t *__restri
   }
 }
 
-// The chunk's range: the last one whose first chunk is at or before `ch` (ranges
-// without candidates own no chunk).
-__device__ __forceinline__ int64_t chunk_range(const int64_t *__restrict__ choff, int64_t R, int64_t ch) {
-  int64_t lo = 0, hi = R;  // first range with choff > ch
-  while (lo < hi) {
-    const int64_t m = (lo + hi) >> 1;
-    if (choff[m] <= ch)
-      lo = m + 1;
-    else
-      hi = m;
-  }
-  return lo - 1;
-}
-
-// first index of the ascending p[0 .. n) with p[i] >= d (UPPER: p[i] > d)
-template <bool UPPER>
-__device__ __forceinline__ int bound(const int32_t *__restrict__ p, int n, int32_t d) {
-  int lo = 0, hi = n;
-  while (lo < hi) {
-    const int m = (lo + hi) >> 1;
-    if (UPPER ? p[m] <= d : p[m] < d)
-      lo = m + 1;
-    else
-      hi = m;
-  }
-  return lo;
-}
 // the posting of document d in docno[start .. start + n), or -1
 __device__ __forceinline__ int64_t find_doc(const int32_t *__restrict__ docno, int64_t start, int n, int32_t d) {
-  const int at = bound<false>(docno + start, n, d);
+  const int at = lower_bound(docno + start, n, d);
   return at < n && docno[start + at] == d ? start + at : -1;
 }
 
-// One workgroup per chunk (grid-stride over the chunks) of at most `chunk`
+// The chunk filter's Op (sme_chunks.hpp): range = slot (driver slots own chunks),
+// candidate c of it the posting sbeg[r] + c, so a chunk is at most `chunk`
 // consecutive postings of one driver slot.  The chunk's docnos lie in [first,
 // last]; per slot of the query the sub-range of its list that can hold such a
 // docno (two bounds) is staged in LDS, with the groups' slot ranges and flags.
 // A required group other than the driver whose sub-ranges are all empty rejects
-// the whole chunk.  Then the candidates are taken kNT at a time, one per thread:
-// every other required group must hold it (OR over the group's slots), no
-// excluded slot may, and one an earlier slot of the driver group also holds is
-// dropped, so a document is emitted once per query.
-// EMIT = false: mcnt[ch] = matches of the chunk.  EMIT = true: at moff[ch] + rank
-// (rank from the waves' ballots) the match's docno, query and score -- the sum
-// from 0.0 of w at its posting over the required slots in listed order.
-template <bool EMIT>
-__global__ __launch_bounds__(kNT) void k_bool_chunks(Batch b, int64_t R, const int64_t *__restrict__ choff, int64_t NC,
-                                                     const int64_t *__restrict__ sbeg,
-                                                     const int32_t *__restrict__ scnt, const int32_t *__restrict__ sq,
-                                                     const int32_t *__restrict__ qdrv,
-                                                     const int32_t *__restrict__ docno, const double *__restrict__ w,
-                                                     int chunk, int64_t *__restrict__ mcnt,
-                                                     const int64_t *__restrict__ moff, int32_t *__restrict__ mdoc,
-                                                     double *__restrict__ mscore, uint32_t *__restrict__ mq) {
-  __shared__ int64_t s_start[boolq::kMaxSlots];
-  __shared__ int32_t s_len[boolq::kMaxSlots];
-  __shared__ int32_t s_gbeg[boolq::kMaxGroups + 1];
-  __shared__ uint8_t s_gflag[boolq::kMaxGroups];
-  __shared__ int s_wsum[kNT / 64];
-  __shared__ int s_reject;
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  for (int64_t ch = blockIdx.x; ch < NC; ch += gridDim.x) {
-    const int64_t r = chunk_range(choff, R, ch);  // the driver slot
-    const int q = sq[r];
-    const int64_t g0 = b.qoff[q];
-    const int ng = (int)(b.qoff[q + 1] - g0);  // <= kMaxGroups (validated on the host)
+// the whole chunk.  A candidate: every other required group must hold it (OR over
+// the group's slots), no excluded slot may, and one an earlier slot of the driver
+// group also holds is dropped, so a document is emitted once per query.  Emitted:
+// the match's docno, query and score -- the sum from 0.0 of w at its posting over
+// the required slots in listed order.
+struct BoolOp {
+  Batch b;
+  const int64_t *sbeg;
+  const int32_t *scnt;
+  const int32_t *sq;
+  const int32_t *qdrv;
+  const int32_t *docno;
+  const double *w;
+  struct Lds {
+    int64_t start[boolq::kMaxSlots];
+    int32_t len[boolq::kMaxSlots];
+    int32_t gbeg[boolq::kMaxGroups + 1];
+    int reject;
+    uint8_t gflag[boolq::kMaxGroups];
+  };
+  struct Chunk {
+    int q, ng, dg, ds;
+    int64_t base;  // the driver slot's first posting
+  };
+  struct Cand {
+    int32_t d;
+  };
+  __device__ __forceinline__ bool stage(Lds &s, Chunk &k, int64_t r, int64_t c0, int len) const {
+    const int tid = threadIdx.x;
+    k.q = sq[r];
+    const int64_t g0 = b.qoff[k.q];
+    k.ng = (int)(b.qoff[k.q + 1] - g0);  // <= kMaxGroups (validated on the host)
     const int64_t s0 = b.goff[g0];
-    const int S = (int)(b.goff[g0 + ng] - s0);  // <= kMaxSlots
-    const int dg = qdrv[q], ds = (int)(r - s0);
-    const int64_t c0 = (ch - choff[r]) * chunk;
-    const int len = (int)min((int64_t)chunk, (int64_t)scnt[r] - c0);  // >= 1
-    const int64_t base = sbeg[r] + c0;
-    const int32_t first = docno[base], last = docno[base + len - 1];
-    if (tid <= ng) s_gbeg[tid] = (int32_t)(b.goff[g0 + tid] - s0);
-    if (tid < ng) s_gflag[tid] = b.gflag[g0 + tid];
-    if (tid == 0) s_reject = 0;
+    const int S = (int)(b.goff[g0 + k.ng] - s0);  // <= kMaxSlots
+    k.dg = qdrv[k.q];
+    k.ds = (int)(r - s0);
+    k.base = sbeg[r];
+    const int32_t first = docno[k.base + c0], last = docno[k.base + c0 + len - 1];
+    if (tid <= k.ng) s.gbeg[tid] = (int32_t)(b.goff[g0 + tid] - s0);
+    if (tid < k.ng) s.gflag[tid] = b.gflag[g0 + tid];
+    if (tid == 0) s.reject = 0;
     for (int j = tid; j < S; j += kNT) {
       const int64_t beg = sbeg[s0 + j];
       const int n = scnt[s0 + j];
-      const int lo = bound<false>(docno + beg, n, first);
-      const int hi = lo + bound<true>(docno + beg + lo, n - lo, last);
-      s_start[j] = beg + lo;
-      s_len[j] = hi - lo;
+      const int lo = lower_bound(docno + beg, n, first);
+      const int hi = lo + upper_bound(docno + beg + lo, n - lo, last);
+      s.start[j] = beg + lo;
+      s.len[j] = hi - lo;
     }
     __syncthreads();
-    if (tid < ng && tid != dg && s_gflag[tid] == 0) {
+    if (tid < k.ng && tid != k.dg && s.gflag[tid] == 0) {
       int any = 0;
-      for (int j = s_gbeg[tid]; j < s_gbeg[tid + 1]; j++) any |= s_len[j];
-      if (any == 0) s_reject = 1;
+      for (int j = s.gbeg[tid]; j < s.gbeg[tid + 1]; j++) any |= s.len[j];
+      if (any == 0) s.reject = 1;
     }
     __syncthreads();
-    const bool reject = s_reject != 0;
-    int64_t run = EMIT ? moff[ch] : 0;  // matches of the rounds before
-    for (int rd = 0; !reject && rd < len; rd += kNT) {
-      const int c = rd + tid;
-      bool hit = false;
-      int32_t d = 0;
-      if (c < len) {
-        d = docno[base + c];
-        hit = true;
-        for (int g = 0; hit && g < ng; g++) {
-          if (g == dg || s_gflag[g] != 0) continue;
-          bool held = false;
-          for (int j = s_gbeg[g]; !held && j < s_gbeg[g + 1]; j++) held = find_doc(docno, s_start[j], s_len[j], d) >= 0;
-          hit = held;
-        }
-        for (int g = 0; hit && g < ng; g++) {
-          if (s_gflag[g] == 0) continue;
-          for (int j = s_gbeg[g]; hit && j < s_gbeg[g + 1]; j++) hit = find_doc(docno, s_start[j], s_len[j], d) < 0;
-        }
-        for (int j = s_gbeg[dg]; hit && j < ds; j++) hit = find_doc(docno, s_start[j], s_len[j], d) < 0;
-      }
-      const unsigned long long m = __ballot(hit);
-      if (lane == 0) s_wsum[wv] = __popcll(m);
-      __syncthreads();
-      int before = 0, total = 0;
-#pragma unroll
-      for (int i = 0; i < kNT / 64; i++) {
-        const int s = s_wsum[i];
-        before += i < wv ? s : 0;
-        total += s;
-      }
-      if (EMIT && hit) {
-        double sc = 0.0;
-        for (int g = 0; g < ng; g++) {
-          if (s_gflag[g] != 0) continue;
-          for (int j = s_gbeg[g]; j < s_gbeg[g + 1]; j++) {
-            const int64_t at = find_doc(docno, s_start[j], s_len[j], d);
-            if (at >= 0) sc += w[at];
-          }
-        }
-        const int64_t at = run + before + __popcll(m & ((1ull << lane) - 1));
-        mdoc[at] = d;
-        mscore[at] = sc;
-        mq[at] = (uint32_t)q;
-      }
-      run += total;
-      __syncthreads();  // s_wsum is rewritten
+    return s.reject == 0;
+  }
+  __device__ __forceinline__ bool test(const Lds &s, const Chunk &k, int64_t, int64_t c, Cand &x) const {
+    const int32_t d = x.d = docno[k.base + c];
+    bool hit = true;
+    for (int g = 0; hit && g < k.ng; g++) {
+      if (g == k.dg || s.gflag[g] != 0) continue;
+      bool held = false;
+      for (int j = s.gbeg[g]; !held && j < s.gbeg[g + 1]; j++) held = find_doc(docno, s.start[j], s.len[j], d) >= 0;
+      hit = held;
     }
-    if (!EMIT && tid == 0) mcnt[ch] = run;
-    __syncthreads();  // the staged query is rewritten
+    for (int g = 0; hit && g < k.ng; g++) {
+      if (s.gflag[g] == 0) continue;
+      for (int j = s.gbeg[g]; hit && j < s.gbeg[g + 1]; j++) hit = find_doc(docno, s.start[j], s.len[j], d) < 0;
+    }
+    for (int j = s.gbeg[k.dg]; hit && j < k.ds; j++) hit = find_doc(docno, s.start[j], s.len[j], d) < 0;
+    return hit;
   }
-}
-
-// woff[i] = matches before query i's first chunk (i = n: all of them); a query's
-// first range is its first slot, and a query without slots has the next one's
-__global__ void k_bool_offs(Batch b, const int64_t *__restrict__ choff, const int64_t *__restrict__ moff, int n,
-                            int64_t *__restrict__ woff) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i <= n; i += (int64_t)gridDim.x * blockDim.x)
-    woff[i] = moff[choff[b.goff[b.qoff[i]]]];
-}
-// kept[i] = query i's matches after the cut (m = 0: no cut); kept[n] = 0
-__global__ void k_bool_cut(const int64_t *__restrict__ woff, int n, int64_t m, int64_t *__restrict__ kept) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i <= n; i += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t c = i < n ? woff[i + 1] - woff[i] : 0;
-    kept[i] = m > 0 && c > m ? m : c;
+  __device__ __forceinline__ void emit(const Lds &s, const Chunk &k, int64_t, const Cand &x, int64_t at,
+                                       int32_t *__restrict__ mdoc, double *__restrict__ mscore,
+                                       uint32_t *__restrict__ mq) const {
+    double sc = 0.0;
+    for (int g = 0; g < k.ng; g++) {
+      if (s.gflag[g] != 0) continue;
+      for (int j = s.gbeg[g]; j < s.gbeg[g + 1]; j++) {
+        const int64_t p = find_doc(docno, s.start[j], s.len[j], x.d);
+        if (p >= 0) sc += w[p];
+      }
+    }
+    mdoc[at] = x.d;
+    mscore[at] = sc;
+    mq[at] = (uint32_t)k.q;
   }
-}
+};
+struct FirstRange {  // query i's first slot; a query without slots has the next one's
+  const int64_t *goff, *qoff;
+  __device__ int64_t operator()(int64_t i) const { return goff[qoff[i]]; }
+};
 // sort keys of the matches: the docno key and the identity permutation ...
 __global__ void k_bool_key_docno(const int32_t *__restrict__ mdoc, int64_t n, uint32_t *__restrict__ key,
                                  uint32_t *__restrict__ perm) {
@@ -273,14 +220,6 @@ __global__ void k_bool_gather(const uint32_t *__restrict__ qs, const uint32_t *_
     out_docno[roff[q] + rk] = mdoc[i];
     out_score[roff[q] + rk] = mscore[i];
   }
-}
-
-// appends an aligned section of `count` T to the upload blob; *at = its byte offset
-template <typename T>
-void section(std::vector<uint8_t> &blob, size_t count, size_t *at) {
-  const size_t a = (blob.size() + alignof(T) - 1) / alignof(T) * alignof(T);
-  blob.resize(a + count * sizeof(T));
-  *at = a;
 }
 }  // namespace
 
@@ -316,16 +255,11 @@ void query_boolean(sme_index *ix, const int32_t *term_ids, const int64_t *g_offs
   const int64_t ng = q_offsets[nq], nt = g_offsets[ng];
   if (nt >= (int64_t(1) << 31)) throw Error(SME_ELIMIT, "boolean batch: 2^31 or more term slots");
   // one upload: slot offsets | group offsets | term ids | flags
-  std::vector<uint8_t> blob;
-  size_t a_goff, a_qoff, a_term, a_flag;
-  section<int64_t>(blob, (size_t)ng + 1, &a_goff);
-  section<int64_t>(blob, (size_t)nq + 1, &a_qoff);
-  section<int32_t>(blob, (size_t)nt, &a_term);
-  section<uint8_t>(blob, (size_t)ng, &a_flag);
-  memcpy(blob.data() + a_goff, g_offsets, ((size_t)ng + 1) * sizeof(int64_t));
-  memcpy(blob.data() + a_qoff, q_offsets, ((size_t)nq + 1) * sizeof(int64_t));
-  if (nt) memcpy(blob.data() + a_term, term_ids, (size_t)nt * sizeof(int32_t));
-  if (ng) memcpy(blob.data() + a_flag, g_flags, (size_t)ng);
+  Blob blob;
+  const size_t a_goff = blob.add(g_offsets, (size_t)ng + 1);
+  const size_t a_qoff = blob.add(q_offsets, (size_t)nq + 1);
+  const size_t a_term = blob.add(term_ids, (size_t)nt);
+  const size_t a_flag = blob.add(g_flags, (size_t)ng);
   const int chunk = (int)cx->opt_bool_chunk;
   const int64_t R = nt;  // one candidate range per slot (driver slots own chunks)
   // temporaries of this call: pooled blocks, back in the pool on return
@@ -334,8 +268,8 @@ void query_boolean(sme_index *ix, const int32_t *term_ids, const int64_t *g_offs
                     &pc, &sa, &sb, &radix})
     b->pool = &cx->pool;
   try {
-    const uint8_t *d_in = in.as<uint8_t>(blob.size());
-    SME_HIP(hipMemcpyAsync((void *)d_in, blob.data(), blob.size(), hipMemcpyHostToDevice, st));
+    const uint8_t *d_in = in.as<uint8_t>(blob.bytes.size());
+    SME_HIP(hipMemcpyAsync((void *)d_in, blob.bytes.data(), blob.bytes.size(), hipMemcpyHostToDevice, st));
     const Batch b{(const int64_t *)(d_in + a_goff), (const int64_t *)(d_in + a_qoff), (const int32_t *)(d_in + a_term),
                   (const uint8_t *)(d_in + a_flag)};
     int64_t *sbeg = sbb.as<int64_t>((size_t)nt);
@@ -351,34 +285,17 @@ void query_boolean(sme_index *ix, const int32_t *term_ids, const int64_t *g_offs
     hipLaunchKernelGGL(k_bool_plan, dim3(grid_for((int64_t)nq + 1)), dim3(kNT), 0, st, b, nq, nt, doff, chunk,
                        (int)cx->opt_bool_driver, sbeg, scnt, sq, qdrv, choff, d_cands);
     SME_CHECK_LAUNCH();
-    excl_scan<int64_t>(choff, choff, R + 1, scn, st);
-    int64_t NC = 0;
     unsigned long long cands = 0;
-    SME_HIP(hipMemcpyAsync(&NC, choff + R, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    SME_HIP(hipMemcpyAsync(&cands, d_cands, sizeof(cands), hipMemcpyDeviceToHost, st));
-    SME_HIP(hipStreamSynchronize(st));
-    // matches per chunk, scanned in place (entry NC = all matches)
-    int64_t *moff = mob.as<int64_t>((size_t)NC + 1);
-    int64_t total = 0;
-    const unsigned cgrid = (unsigned)std::max<int64_t>(1, std::min(NC, kMaxGrid));
-    SME_HIP(hipMemsetAsync(moff + NC, 0, sizeof(int64_t), st));
-    if (NC > 0) {
-      hipLaunchKernelGGL(k_bool_chunks<false>, dim3(cgrid), dim3(kNT), 0, st, b, R, (const int64_t *)choff, NC,
-                         (const int64_t *)sbeg, (const int32_t *)scnt, (const int32_t *)sq, (const int32_t *)qdrv, docno,
-                         w, chunk, moff, (const int64_t *)nullptr, (int32_t *)nullptr, (double *)nullptr,
-                         (uint32_t *)nullptr);
-      SME_CHECK_LAUNCH();
-      excl_scan<int64_t>(moff, moff, NC + 1, scn, st);
-      SME_HIP(hipMemcpyAsync(&total, moff + NC, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-      SME_HIP(hipStreamSynchronize(st));
-    }
-    if (total >= (int64_t(1) << 31)) throw Error(SME_ELIMIT, "boolean: 2^31 or more matches in one batch");
+    const BoolOp op{b, sbeg, scnt, sq, qdrv, docno, w};
+    const Counted c = count_chunks(op, (int)R, choff, scnt, chunk, mob, scn,
+                                   "boolean: 2^31 or more matches in one batch", st, d_cands, &cands);
+    const int64_t total = c.total;
     int64_t *woff = wob.as<int64_t>((size_t)nq + 1);
     int64_t *kept = kpb.as<int64_t>((size_t)nq + 1);
-    hipLaunchKernelGGL(k_bool_offs, dim3(grid_for((int64_t)nq + 1)), dim3(kNT), 0, st, b, (const int64_t *)choff,
-                       (const int64_t *)moff, nq, woff);
-    hipLaunchKernelGGL(k_bool_cut, dim3(grid_for((int64_t)nq + 1)), dim3(kNT), 0, st, (const int64_t *)woff, nq, (int64_t)m,
-                       kept);
+    hipLaunchKernelGGL(k_owner_offs<FirstRange>, dim3(grid_for((int64_t)nq + 1)), dim3(kNT), 0, st,
+                       FirstRange{b.goff, b.qoff}, c.choff, c.moff, (int64_t)nq, woff);
+    hipLaunchKernelGGL(k_cut, dim3(grid_for((int64_t)nq + 1)), dim3(kNT), 0, st, (const int64_t *)woff, (int64_t)nq,
+                       (int64_t)m, kept);
     SME_CHECK_LAUNCH();
     excl_scan<int64_t>(kept, d_roff, (int64_t)nq + 1, scn, st);
     int64_t out_total = 0;
@@ -393,10 +310,7 @@ void query_boolean(sme_index *ix, const int32_t *term_ids, const int64_t *g_offs
       uint32_t *mq = mqb.as<uint32_t>(T);
       uint32_t *k0 = ka.as<uint32_t>(T), *k1 = kb.as<uint32_t>(T);
       uint32_t *p0 = pa.as<uint32_t>(T), *p1 = pb.as<uint32_t>(T);
-      hipLaunchKernelGGL(k_bool_chunks<true>, dim3(cgrid), dim3(kNT), 0, st, b, R, (const int64_t *)choff, NC,
-                         (const int64_t *)sbeg, (const int32_t *)scnt, (const int32_t *)sq, (const int32_t *)qdrv, docno,
-                         w, chunk, (int64_t *)nullptr, (const int64_t *)moff, mdoc, mscore, mq);
-      SME_CHECK_LAUNCH();
+      emit_chunks(op, c, st, mdoc, mscore, mq);
       // least significant key first, every pass stable: docno, (score,) query
       const unsigned g = grid_for(total);
       hipLaunchKernelGGL(k_bool_key_docno, dim3(g), dim3(kNT), 0, st, (const int32_t *)mdoc, total, k0, p0);
@@ -412,9 +326,7 @@ void query_boolean(sme_index *ix, const int32_t *term_ids, const int64_t *g_offs
       }
       hipLaunchKernelGGL(k_bool_key_query, dim3(g), dim3(kNT), 0, st, (const uint32_t *)mq, (const uint32_t *)perm,
                          total, k0);
-      int qbits = 1;
-      while (qbits < 32 && (int64_t(1) << qbits) < nq) qbits++;
-      sort_pairs<uint32_t>(k0, k1, perm, spare, total, qbits, radix, st);
+      sort_pairs<uint32_t>(k0, k1, perm, spare, total, owner_bits(nq), radix, st);
       hipLaunchKernelGGL(k_bool_gather, dim3(g), dim3(kNT), 0, st, (const uint32_t *)k1, (const uint32_t *)spare,
                          (const int32_t *)mdoc, (const double *)mscore, total, (const int64_t *)woff,
                          (const int64_t *)d_roff, (int64_t)m, out_docno, out_score);

@@ -10,9 +10,9 @@
 //
 // Expansion: k_wild_plan picks per pattern the shortest posting list among its
 // trigrams (or the whole vocabulary), the candidates are cut into chunks, and
-// k_wild_chunks -- once counting, once emitting -- verifies every candidate with
-// wild_match, one workgroup per chunk: the candidate source never changes the
-// result.
+// the chunk filter of sme_chunks.hpp -- once counting, once emitting -- verifies
+// every candidate with wild_match (WildOp), one workgroup per chunk: the candidate
+// source never changes the result.
 #include <hip/hip_runtime.h>
 #include <string.h>
 
@@ -20,15 +20,13 @@
 #include <string>
 #include <vector>
 
+#include "sme_chunks.hpp"
 #include "sme_internal.hpp"
 #include "sme_wild.hpp"
 
 namespace sme {
 namespace {
-constexpr int kNT = 256;  // threads of the chunk kernels
-constexpr int64_t kMaxGrid = 1 << 20;
-
-unsigned grid_for(int64_t n) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + kNT - 1) / kNT, 65536)); }
+using namespace chunks;
 
 // ---- table build ------------------------------------------------------------
 // A term of L units has L windows, so the windows' exclusive scan is the term
@@ -39,15 +37,7 @@ __global__ void k_wt_pairs(const int64_t *__restrict__ toff, const uint16_t *__r
   const int64_t base = toff[0];
   for (int64_t w = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; w < NP; w += (int64_t)gridDim.x * blockDim.x) {
     const int64_t pos = base + w;
-    int64_t lo = 0, hi = V;  // first term with toff > pos
-    while (lo < hi) {
-      const int64_t m = (lo + hi) >> 1;
-      if (toff[m] <= pos)
-        lo = m + 1;
-      else
-        hi = m;
-    }
-    const int64_t t = lo - 1, b = toff[t];
+    const int64_t t = upper_bound(toff, V, pos) - 1, b = toff[t];
     keys[w] = wild::term_gram(tch + b, toff[t + 1] - b, pos - b);
     vals[w] = (uint32_t)t;
   }
@@ -104,24 +94,15 @@ __global__ void k_wild_plan(Batch b, int n, const uint64_t *__restrict__ keys, c
     int32_t beg = -1, cnt = (int32_t)V;
     if (!scan) {
       for (int g = b.goff[i]; g < b.goff[i + 1]; g++) {
-        const uint64_t k = b.gkey[g];
-        int64_t lo = 0, hi = G;  // first key >= k
-        while (lo < hi) {
-          const int64_t m = (lo + hi) >> 1;
-          if (keys[m] < k)
-            lo = m + 1;
-          else
-            hi = m;
-        }
-        if (lo == G || keys[lo] != k) {  // a trigram no term holds: no match
+        const GramRange p = gram_postings(keys, goff, G, b.gkey[g]);
+        if (p.cnt == 0) {  // a trigram no term holds: no match
           beg = 0;
           cnt = 0;
           break;
         }
-        const int32_t c = goff[lo + 1] - goff[lo];
-        if (beg < 0 || c < cnt) {
-          beg = goff[lo];
-          cnt = c;
+        if (beg < 0 || p.cnt < cnt) {
+          beg = p.beg;
+          cnt = p.cnt;
         }
       }
     }
@@ -131,89 +112,51 @@ __global__ void k_wild_plan(Batch b, int n, const uint64_t *__restrict__ keys, c
   }
 }
 
-// The chunk's pattern: the last one whose first chunk is at or before `ch`
-// (patterns without candidates own no chunk).
-__device__ __forceinline__ int chunk_pattern(const int64_t *__restrict__ choff, int n, int64_t ch) {
-  int lo = 0, hi = n;  // first pattern with choff > ch
-  while (lo < hi) {
-    const int m = (lo + hi) >> 1;
-    if (choff[m] <= ch)
-      lo = m + 1;
-    else
-      hi = m;
-  }
-  return lo - 1;
-}
-
-// One workgroup per chunk (grid-stride over the chunks): the pattern is staged in
-// LDS, the chunk's candidates are taken kNT at a time, one per thread.  EMIT = false:
-// mcnt[ch] = matches of the chunk.  EMIT = true: the matches' term ids at
-// moff[ch] + rank, the rank from the waves' ballots, so they come out ascending.
-template <bool EMIT>
-__global__ __launch_bounds__(kNT) void k_wild_chunks(Batch b, int n, const int64_t *__restrict__ choff, int64_t NC,
-                                                     const int32_t *__restrict__ cbeg,
-                                                     const int32_t *__restrict__ ccnt,
-                                                     const int32_t *__restrict__ gterm,
-                                                     const int64_t *__restrict__ toff,
-                                                     const uint16_t *__restrict__ tch, int chunk,
-                                                     int64_t *__restrict__ mcnt, const int64_t *__restrict__ moff,
-                                                     int32_t *__restrict__ ids) {
-  __shared__ uint16_t s_unit[256];
-  __shared__ uint8_t s_mask[256];
-  __shared__ int s_wsum[kNT / 64];
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  for (int64_t ch = blockIdx.x; ch < NC; ch += gridDim.x) {
-    const int i = chunk_pattern(choff, n, ch);
-    const int u0 = b.uoff[i], np = b.uoff[i + 1] - u0;
-    if (tid < np) {
-      s_unit[tid] = b.unit[u0 + tid];
-      s_mask[tid] = b.mask[u0 + tid];
+// The chunk filter's Op (sme_chunks.hpp): range = pattern, candidate c of it the
+// term id c (beg < 0) or gterm[beg + c].  The pattern is staged in LDS, a hit is a
+// term wild_match accepts, and its term id is emitted: ids come out ascending.
+struct WildOp {
+  Batch b;
+  const int32_t *cbeg;
+  const int32_t *gterm;
+  const int64_t *toff;
+  const uint16_t *tch;
+  struct Lds {
+    uint16_t unit[256];
+    uint8_t mask[256];
+  };
+  struct Chunk {
+    int np;
+    int32_t beg;
+  };
+  struct Cand {
+    int32_t t;
+  };
+  __device__ __forceinline__ bool stage(Lds &s, Chunk &k, int64_t i, int64_t, int) const {
+    const int tid = threadIdx.x;
+    const int u0 = b.uoff[i];
+    k.np = b.uoff[i + 1] - u0;
+    k.beg = cbeg[i];
+    if (tid < k.np) {
+      s.unit[tid] = b.unit[u0 + tid];
+      s.mask[tid] = b.mask[u0 + tid];
     }
     __syncthreads();
-    const int32_t beg = cbeg[i];
-    const int64_t c0 = (ch - choff[i]) * chunk;
-    const int len = (int)min((int64_t)chunk, (int64_t)ccnt[i] - c0);
-    int64_t run = EMIT ? moff[ch] : 0;  // matches of the rounds before
-    for (int r = 0; r < len; r += kNT) {
-      const int c = r + tid;
-      bool hit = false;
-      int32_t t = 0;
-      if (c < len) {
-        t = beg < 0 ? (int32_t)(c0 + c) : gterm[beg + c0 + c];
-        const int64_t a = toff[t];
-        hit = wild::wild_match(s_unit, s_mask, np, tch + a, (int)(toff[t + 1] - a));
-      }
-      const unsigned long long m = __ballot(hit);
-      if (lane == 0) s_wsum[wv] = __popcll(m);
-      __syncthreads();
-      int before = 0, total = 0;
-#pragma unroll
-      for (int w = 0; w < kNT / 64; w++) {
-        const int s = s_wsum[w];
-        before += w < wv ? s : 0;
-        total += s;
-      }
-      if (EMIT && hit) ids[run + before + __popcll(m & ((1ull << lane) - 1))] = t;
-      run += total;
-      __syncthreads();  // s_wsum (and, after the last round, the staged pattern) is rewritten
-    }
-    if (!EMIT && tid == 0) mcnt[ch] = run;
+    return true;
   }
-}
-
-// match_off[i] = matches before pattern i's first chunk (i = n: all of them)
-__global__ void k_wild_offs(const int64_t *__restrict__ choff, const int64_t *__restrict__ moff, int n,
-                            int64_t *__restrict__ out) {
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i <= n; i += gridDim.x * blockDim.x) out[i] = moff[choff[i]];
-}
-
-// appends an aligned section of `count` T to the upload blob; *at = its byte offset
-template <typename T>
-void section(std::vector<uint8_t> &blob, size_t count, size_t *at) {
-  const size_t a = (blob.size() + alignof(T) - 1) / alignof(T) * alignof(T);
-  blob.resize(a + count * sizeof(T));
-  *at = a;
-}
+  __device__ __forceinline__ bool test(const Lds &s, const Chunk &k, int64_t, int64_t c, Cand &x) const {
+    x.t = k.beg < 0 ? (int32_t)c : gterm[k.beg + c];
+    const int64_t a = toff[x.t];
+    return wild::wild_match(s.unit, s.mask, k.np, tch + a, (int)(toff[x.t + 1] - a));
+  }
+  __device__ __forceinline__ void emit(const Lds &, const Chunk &, int64_t, const Cand &x, int64_t at,
+                                       int32_t *__restrict__ ids) const {
+    ids[at] = x.t;
+  }
+};
+struct FirstRange {  // pattern i's first (and only) range
+  __device__ int64_t operator()(int64_t i) const { return i; }
+};
 }  // namespace
 
 void prepare_wildcards(sme_index *ix, hipStream_t st) {
@@ -327,23 +270,17 @@ void expand_wildcards(sme_index *ix, const uint8_t *patterns, const int64_t *off
   }
   if (!cx->opt_wild_scan) prepare_wildcards(ix, st);
   // one upload: gram keys | unit offsets | gram offsets | units | masks
-  std::vector<uint8_t> blob;
-  size_t a_key, a_uoff, a_goff, a_unit, a_mask;
-  section<uint64_t>(blob, gkeys.size(), &a_key);
-  section<int32_t>(blob, uoff.size(), &a_uoff);
-  section<int32_t>(blob, goff.size(), &a_goff);
-  section<uint16_t>(blob, units.size(), &a_unit);
-  section<uint8_t>(blob, mask.size(), &a_mask);
-  if (!gkeys.empty()) memcpy(blob.data() + a_key, gkeys.data(), gkeys.size() * sizeof(uint64_t));
-  memcpy(blob.data() + a_uoff, uoff.data(), uoff.size() * sizeof(int32_t));
-  memcpy(blob.data() + a_goff, goff.data(), goff.size() * sizeof(int32_t));
-  if (!units.empty()) memcpy(blob.data() + a_unit, units.data(), units.size() * sizeof(uint16_t));
-  if (!mask.empty()) memcpy(blob.data() + a_mask, mask.data(), mask.size());
-  const uint8_t *d_in = ix->d_wx_in.as<uint8_t>(blob.size());
+  Blob blob;
+  const size_t a_key = blob.add(gkeys.data(), gkeys.size());
+  const size_t a_uoff = blob.add(uoff.data(), uoff.size());
+  const size_t a_goff = blob.add(goff.data(), goff.size());
+  const size_t a_unit = blob.add(units.data(), units.size());
+  const size_t a_mask = blob.add(mask.data(), mask.size());
+  const uint8_t *d_in = ix->d_wx_in.as<uint8_t>(blob.bytes.size());
   const int chunk = (int)cx->opt_wild_chunk;
   const int64_t V = ix->V;
   try {
-    SME_HIP(hipMemcpyAsync((void *)d_in, blob.data(), blob.size(), hipMemcpyHostToDevice, st));
+    SME_HIP(hipMemcpyAsync((void *)d_in, blob.bytes.data(), blob.bytes.size(), hipMemcpyHostToDevice, st));
     const Batch b{(const uint64_t *)(d_in + a_key), (const int32_t *)(d_in + a_uoff), (const int32_t *)(d_in + a_goff),
                   (const uint16_t *)(d_in + a_unit), d_in + a_mask};
     // per pattern: candidate range (2 x int32) and chunk offsets (int64)
@@ -354,40 +291,16 @@ void expand_wildcards(sme_index *ix, const uint8_t *patterns, const int64_t *off
                        (const int32_t *)ix->d_wgoff.p, cx->opt_wild_scan ? 0 : ix->wild_G, V, (int)cx->opt_wild_scan,
                        chunk, cbeg, ccnt, choff);
     SME_CHECK_LAUNCH();
-    excl_scan<int64_t>(choff, choff, (int64_t)n + 1, ix->d_wx_scan, st);
-    int64_t NC = 0;
-    SME_HIP(hipMemcpyAsync(&NC, choff + n, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    SME_HIP(hipStreamSynchronize(st));
-    // matches per chunk, scanned in place (entry NC = all matches)
-    int64_t *moff = ix->d_wx_moff.as<int64_t>((size_t)NC + 1);
-    int64_t total = 0;
-    const unsigned cgrid = (unsigned)std::max<int64_t>(1, std::min(NC, kMaxGrid));
-    const int64_t *toff = (const int64_t *)ix->d_term_off.p;
-    const uint16_t *tch = (const uint16_t *)ix->d_term_chars.p;
-    const int32_t *gterm = (const int32_t *)ix->d_wgterm.p;
-    SME_HIP(hipMemsetAsync(moff + NC, 0, sizeof(int64_t), st));
-    if (NC > 0) {
-      hipLaunchKernelGGL(k_wild_chunks<false>, dim3(cgrid), dim3(kNT), 0, st, b, n, (const int64_t *)choff, NC,
-                         (const int32_t *)cbeg, (const int32_t *)ccnt, gterm, toff, tch, chunk, moff,
-                         (const int64_t *)nullptr, (int32_t *)nullptr);
-      SME_CHECK_LAUNCH();
-      excl_scan<int64_t>(moff, moff, NC + 1, ix->d_wx_scan, st);
-      SME_HIP(hipMemcpyAsync(&total, moff + NC, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-      SME_HIP(hipStreamSynchronize(st));
-    }
-    if (total >= (int64_t(1) << 31)) throw Error(SME_ELIMIT, "wildcard expansion: 2^31 or more matches in one batch");
-    int32_t *ids = ix->d_wx_ids.as<int32_t>((size_t)total);
-    if (total > 0) {
-      hipLaunchKernelGGL(k_wild_chunks<true>, dim3(cgrid), dim3(kNT), 0, st, b, n, (const int64_t *)choff, NC,
-                         (const int32_t *)cbeg, (const int32_t *)ccnt, gterm, toff, tch, chunk, (int64_t *)nullptr,
-                         (const int64_t *)moff, ids);
-      SME_CHECK_LAUNCH();
-    }
-    hipLaunchKernelGGL(k_wild_offs, dim3(grid_for(n + 1)), dim3(kNT), 0, st, (const int64_t *)choff,
-                       (const int64_t *)moff, n, d_moffs);
+    const WildOp op{b, cbeg, (const int32_t *)ix->d_wgterm.p, (const int64_t *)ix->d_term_off.p,
+                    (const uint16_t *)ix->d_term_chars.p};
+    const Counted c = count_chunks(op, n, choff, ccnt, chunk, ix->d_wx_moff, ix->d_wx_scan,
+                                   "wildcard expansion: 2^31 or more matches in one batch", st);
+    emit_chunks(op, c, st, ix->d_wx_ids.as<int32_t>((size_t)c.total));
+    hipLaunchKernelGGL(k_owner_offs<FirstRange>, dim3(grid_for(n + 1)), dim3(kNT), 0, st, FirstRange{}, c.choff,
+                       c.moff, (int64_t)n, d_moffs);
     SME_CHECK_LAUNCH();
     SME_HIP(hipStreamSynchronize(st));
-    ix->wx_total = total;
+    ix->wx_total = c.total;
   } catch (...) {
     (void)hipStreamSynchronize(st);  // the upload may still read `blob`
     throw;

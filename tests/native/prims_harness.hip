@@ -21,51 +21,15 @@
 #include <string>
 #include <vector>
 
+#include "prims_guard.hpp"
 #include "sme_internal.hpp"
 
 namespace {
-
-constexpr size_t kGuard = 256 * 8;
-constexpr int kFill = 0xA5;
+using smep::GBuf;
+using smep::kFill;
+using smep::kGuard;
 
 std::string g_err;
-
-struct GBuf {  // device buffer of `bytes` payload + guard, all 0xA5 at first
-  uint8_t *p = nullptr;
-  size_t bytes = 0;
-  explicit GBuf(size_t b) : bytes(b) {
-    const hipError_t e = hipMalloc(reinterpret_cast<void **>(&p), bytes + kGuard);
-    if (e != hipSuccess) {
-      p = nullptr;
-      (void)hipGetLastError();
-      throw sme::Error(e == hipErrorOutOfMemory ? SME_ENOMEM : SME_EHIP,
-                       std::string("harness hipMalloc: ") + hipGetErrorString(e));
-    }
-    SME_HIP(hipMemset(p, kFill, bytes + kGuard));
-  }
-  GBuf(const GBuf &) = delete;
-  GBuf &operator=(const GBuf &) = delete;
-  ~GBuf() {
-    if (p) (void)hipFree(p);
-  }
-  template <typename T>
-  T *as() const {
-    return reinterpret_cast<T *>(p);
-  }
-  void put(const void *h, size_t n) {
-    if (h && n) SME_HIP(hipMemcpy(p, h, std::min(n, bytes), hipMemcpyHostToDevice));
-  }
-  void get(void *h, size_t n) const {
-    if (h && n) SME_HIP(hipMemcpy(h, p, std::min(n, bytes), hipMemcpyDeviceToHost));
-  }
-  bool guard_changed() const {
-    uint8_t g[kGuard];
-    SME_HIP(hipMemcpy(g, p + bytes, kGuard, hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < kGuard; i++)
-      if (g[i] != (uint8_t)kFill) return true;
-    return false;
-  }
-};
 
 struct Stream {
   hipStream_t s = nullptr;
