@@ -146,6 +146,10 @@ void sme_destroy(sme_ctx *ctx);
  *   "bool_chunk"    Boolean-query candidates per workgroup, 64..4096 in multiples of 64 (default 1024)
  *   "bool_driver"   Boolean queries: 0 (default) the required group with the fewest postings
  *                   supplies the candidates, 1 the first required group
+ *   "positions"     0 (default): nothing is kept; 1: a K = 1 sme_build_index* also keeps every
+ *                   record's term stream with the index (sme_index_positions), which phrase
+ *                   queries (sme_query_phrase) need.  Every other output of the build is the
+ *                   same bytes; "bool_chunk" also cuts a phrase query's candidates
  * Unknown names and out-of-range values are SME_EINVAL. */
 int sme_set_option(sme_ctx *ctx, const char *name, int64_t value);
 
@@ -418,6 +422,65 @@ int sme_query_boolean_device(sme_index *ix, const int32_t *term_ids, const int64
                              const int64_t **d_res_off, const int32_t **d_docno, const double **d_score,
                              int64_t *total);
 int sme_query_boolean_stats(const sme_index *ix, uint64_t *candidates, uint64_t *matches);
+
+/* Positions: what a K = 1 index built with option "positions" 1 keeps beside its
+ * postings -- per record, in docno-ascending record order, the term ids
+ * (sme_lookup_terms' ids) of its tokens in token order, after stop-wording,
+ * stemming and the expansion of tokens that give several terms, the DOCNO's
+ * tokens included: a forward index.  Records that share a docno (duplicate
+ * docids, docno 0 of records without DOCNO, the negative docnos of docids missing
+ * from the mapping) stay separate records.  *records = stream records, *positions
+ * = term positions over all of them, *bytes = device memory they take; all three
+ * 0 for an index that keeps none: one built without the option or with K >= 2, a
+ * chargram output, and every index from sme_index_from_records* or
+ * sme_merge_pieces -- positions cannot be added to an index later. */
+int sme_index_positions(const sme_index *ix, uint64_t *records, uint64_t *positions, uint64_t *bytes);
+
+/* Phrase queries (no reference counterpart; the reference answers a phrase of m
+ * terms from a second index built with K = m).  Phrase i is the term ids
+ * term_ids[p_offsets[i] .. p_offsets[i + 1]) (np + 1 entries from 0), L of them;
+ * host arrays.  Document d matches with freq = the number of pairs (record r with
+ * docno d, start s) such that s + L <= the length of r's term stream and
+ * stream_r[s + j] == phrase[j] for every j < L.  Overlapping occurrences all
+ * count ("a a" in "a a a": 2), an occurrence never crosses a record's end, and
+ * freq sums over all records of the docno.  That is the posting (d, freq) of the
+ * gram in the reference's K = L index of the same corpus.  A phrase holding id
+ * -1 (an unknown term) and an empty phrase have no result; an id outside [-1, V)
+ * is SME_EINVAL, more than 32 terms SME_ELIMIT (both messages name the phrase).
+ * score = (1 + ln freq) * idf(df), one fp64 product, with df = the phrase's
+ * matching documents BEFORE the cut and idf the expression of the index's weights
+ * (log10(N / 1) in SME_IDF_REFERENCE, log10(N / df) with the integer quotient
+ * otherwise; N as of the last sme_index_reweight, the df always this index's
+ * own): the bits of d_weight at the gram's posting in a K = L index built by a
+ * context with the same settings.  order 0: a phrase's results by docno ascending
+ * (signed int32 order); order 1: by score descending, then docno ascending; both
+ * then cut to the first m entries (m == 0: no cut).  Phrase i's results are
+ * docno[] / freq[] / score[] at [res_off[i], res_off[i + 1]); np + 1 offsets,
+ * owned by the index until the next phrase call on it (host memory from the host
+ * entry; device memory from the device entry, with *total = res_off[np], total
+ * may be NULL).  A phrase call leaves the buffers of the last wildcard, suggestion
+ * and Boolean call alone, and the other way round.  np == 0 is valid.
+ * Limits: 2^31 or more term slots in a batch, and 2^31 or more documents holding
+ * all terms of their phrase over a batch (BEFORE positions are looked at and
+ * before the cut) are SME_ELIMIT.  p_offsets is never NULL when np > 0; term_ids
+ * may be NULL only in a batch without a term.  m < 0, an order other than 0 / 1
+ * and offsets that do not ascend from 0 are SME_EINVAL.  SME_EINVAL, with a
+ * message that says which, is also: an index without positions (see
+ * sme_index_positions), one with K != 1, one without a query side, a chargram
+ * output.
+ * Candidates come from the phrase's term with the fewest postings; each is tested
+ * against the posting lists of the phrase's other distinct terms, and the
+ * survivors' records are scanned.  sme_query_phrase_stats reports on the last
+ * phrase call on the index: *candidates = the driver postings examined,
+ * *verified = the (phrase, document) pairs that hold all the phrase's terms and
+ * had their records scanned, *matches = those with freq > 0, the matches before
+ * the cut. */
+int sme_query_phrase(sme_index *ix, const int32_t *term_ids, const int64_t *p_offsets, int np, int order, int m,
+                     const int64_t **res_off, const int32_t **docno, const int32_t **freq, const double **score);
+int sme_query_phrase_device(sme_index *ix, const int32_t *term_ids, const int64_t *p_offsets, int np, int order,
+                            int m, void *stream, const int64_t **d_res_off, const int32_t **d_docno,
+                            const int32_t **d_freq, const double **d_score, int64_t *total);
+int sme_query_phrase_stats(const sme_index *ix, uint64_t *candidates, uint64_t *verified, uint64_t *matches);
 
 /* Batched rank(): query q has term ids term_ids[q_offsets[q] .. q_offsets[q+1])
  * in query-token order (duplicates count twice, -1 entries are skipped; an id

@@ -56,6 +56,7 @@ EXPORTS = [
     "sme_index_expand_wildcards_device",
     "sme_index_suggest_terms", "sme_index_suggest_terms_device", "sme_index_suggest_stats",
     "sme_query_boolean", "sme_query_boolean_device", "sme_query_boolean_stats",
+    "sme_index_positions", "sme_query_phrase", "sme_query_phrase_device", "sme_query_phrase_stats",
 ]
 
 
@@ -146,6 +147,12 @@ def lib():
     L.sme_query_boolean_device.argtypes = [vp, i32p, i64p, u8p, i64p, C.c_int, C.c_int, C.c_int, vp, C.POINTER(vp),
                                            C.POINTER(vp), C.POINTER(vp), i64p]
     L.sme_query_boolean_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.sme_index_positions.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.sme_query_phrase.argtypes = [vp, i32p, i64p, C.c_int, C.c_int, C.c_int, C.POINTER(i64p), C.POINTER(i32p),
+                                   C.POINTER(i32p), C.POINTER(f64p)]
+    L.sme_query_phrase_device.argtypes = [vp, i32p, i64p, C.c_int, C.c_int, C.c_int, vp, C.POINTER(vp), C.POINTER(vp),
+                                          C.POINTER(vp), C.POINTER(vp), i64p]
+    L.sme_query_phrase_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     _lib = L
     return L
 
@@ -649,6 +656,77 @@ class Index:
         _check(lib().sme_query_boolean_stats(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
 
+    def positions(self):
+        """sme_index_positions: (records, positions, bytes) of the term streams the
+        index keeps for phrase queries -- all zero unless it is a K = 1 index built
+        with Context.set_option("positions", 1)."""
+        a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        _check(lib().sme_index_positions(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
+
+    @staticmethod
+    def phrase_arrays(phrases):
+        """The C-ABI's structure of a list of phrases, each a list of term ids:
+        (term_ids int32, p_offsets int64[np+1])."""
+        terms, poff = [], [0]
+        for ph in phrases:
+            terms.extend(int(t) for t in ph)
+            poff.append(len(terms))
+        return np.array(terms, np.int32), np.array(poff, np.int64)
+
+    @staticmethod
+    def _phrase_ptrs(term_ids, p_offsets):
+        # (an empty numpy array may hand out any pointer: keep one element behind each)
+        t = np.ascontiguousarray(term_ids, dtype=np.int32)
+        o = np.ascontiguousarray(p_offsets, dtype=np.int64)
+        t = t if t.size else np.zeros(1, np.int32)
+        o = o if o.size else np.zeros(1, np.int64)
+        return (t, o), (t.ctypes.data_as(C.POINTER(C.c_int32)), o.ctypes.data_as(C.POINTER(C.c_int64)))
+
+    def query_phrase(self, phrases, order=0, m=0, arrays=None):
+        """sme_query_phrase: phrases = a list of phrases, each a list of term ids
+        (Index.lookup's; -1 = unknown, the phrase then has no result).  A document
+        matches a phrase when a record of it holds the terms at consecutive
+        positions; freq counts those places (overlaps included, summed over the
+        docno's records), score = (1 + ln freq) * idf(matching documents), the
+        weight a K = len(phrase) index gives that gram.  Returns (res_off
+        int64[np+1], docno int32, freq int32, score float64): phrase i's matches
+        are [res_off[i], res_off[i+1]), by docno ascending (order 0) or score
+        descending then docno ascending (order 1), cut to the first m (0: no cut)
+        (include/sme.h).  The index must keep positions (Index.positions).
+        arrays: the structure as phrase_arrays returns it, instead of phrases."""
+        t, o = arrays if arrays is not None else Index.phrase_arrays(phrases)
+        n = len(o) - 1
+        keep, ptrs = Index._phrase_ptrs(t, o)
+        ro, dn, fq, sc = C.POINTER(C.c_int64)(), C.POINTER(C.c_int32)(), C.POINTER(C.c_int32)(), C.POINTER(C.c_double)()
+        _check(lib().sme_query_phrase(self._h, *ptrs, n, int(order), int(m), C.byref(ro), C.byref(dn), C.byref(fq),
+                                      C.byref(sc)))
+        off = np.ctypeslib.as_array(ro, (n + 1,)).copy()
+        total = int(off[n])
+        docno = np.ctypeslib.as_array(dn, (total,)).copy() if total else np.zeros(0, np.int32)
+        freq = np.ctypeslib.as_array(fq, (total,)).copy() if total else np.zeros(0, np.int32)
+        score = np.ctypeslib.as_array(sc, (total,)).copy() if total else np.zeros(0, np.float64)
+        return off, docno, freq, score
+
+    def query_phrase_device(self, phrases, order=0, m=0, stream=None, arrays=None):
+        """sme_query_phrase_device: (device pointer of res_off int64[np+1], of docno
+        int32[total], of freq int32[total], of score float64[total], total); the
+        arrays belong to the index until its next phrase call."""
+        t, o = arrays if arrays is not None else Index.phrase_arrays(phrases)
+        keep, ptrs = Index._phrase_ptrs(t, o)
+        ro, dn, fq, sc, tot = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int64()
+        _check(lib().sme_query_phrase_device(self._h, *ptrs, len(o) - 1, int(order), int(m), C.c_void_p(stream or 0),
+                                             C.byref(ro), C.byref(dn), C.byref(fq), C.byref(sc), C.byref(tot)))
+        return ro.value or 0, dn.value or 0, fq.value or 0, sc.value or 0, tot.value
+
+    def phrase_stats(self):
+        """(candidates, verified, matches) of the last phrase call: the driver
+        postings examined, the (phrase, document) pairs whose records were
+        scanned, and the matches before the cut."""
+        a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        _check(lib().sme_query_phrase_stats(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
+
     def reweight(self, n_global, d_df_global=None, stream=None):
         """TF-IDF weights with all-reduced N (and df) of a doc-sharded index."""
         _check(lib().sme_index_reweight(self._h, n_global, C.c_void_p(d_df_global or 0), C.c_void_p(stream or 0)))
@@ -887,6 +965,21 @@ class IntDocVectorsForwardIndex:
     def rank_boolean(self, k=10):
         """The first k documents (score desc, docno asc) matching get_boolean's groups."""
         _, dn, _ = self.index.query_boolean([getattr(self, "_groups", [])], order=1, m=k)
+        return [int(d) for d in dn]
+
+    def get_phrase(self, text):
+        """An exact phrase from a text: processContent (stop words are dropped as
+        the indexer drops them, so the phrase is what the indexer saw of the
+        text) -> the term lookup -> one phrase for rank_phrase(); an unknown
+        token stays as -1, so the phrase then has no results.  Returns the term
+        ids.  The index must keep positions (Index.positions)."""
+        toks = self.index.ctx.process_content(text)
+        self._phrase = [int(t) for t in self.index.lookup(toks)] if toks else []
+        return self._phrase
+
+    def rank_phrase(self, k=10):
+        """The first k documents (score desc, docno asc) holding get_phrase's phrase."""
+        _, dn, _, _ = self.index.query_phrase([getattr(self, "_phrase", [])], order=1, m=k)
         return [int(d) for d in dn]
 
     def rank(self, k=10):

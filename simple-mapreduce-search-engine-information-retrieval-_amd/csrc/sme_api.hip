@@ -353,6 +353,9 @@ int sme_set_option(sme_ctx *cx, const char *name, int64_t v) {
     } else if (n == "bool_driver") {
       range(0, 1);
       cx->opt_bool_driver = v;
+    } else if (n == "positions") {
+      range(0, 1);
+      cx->opt_positions = v;
     } else {
       throw sme::Error(SME_EINVAL, "unknown option " + n);
     }
@@ -905,6 +908,90 @@ int sme_query_boolean_stats(const sme_index *ix, uint64_t *candidates, uint64_t 
     if (!ix || !candidates || !matches) throw sme::Error(SME_EINVAL, "null argument");
     *candidates = ix->bq_cands;
     *matches = ix->bq_matches;
+  });
+}
+
+// Phrase queries run over the query side and the positions of a K = 1 index
+static void need_phrase_args(const sme_index *ix, const int32_t *term_ids, const int64_t *p_offsets, int np, int order,
+                             int m) {
+  if (!ix || np < 0 || (np > 0 && !p_offsets)) throw sme::Error(SME_EINVAL, "bad argument");
+  if (ix->job != 0) throw sme::Error(SME_EINVAL, "phrase query: not a TermKGramDocIndexer index");
+  if (ix->records_only)
+    throw sme::Error(SME_EINVAL, "phrase query: the index has no query side (merged shard pieces)");
+  if (ix->K != 1) throw sme::Error(SME_EINVAL, "phrase query: the index holds k-grams (K != 1), not terms");
+  if (!ix->has_positions)
+    throw sme::Error(SME_EINVAL, "phrase query: the index keeps no positions (build it with option \"positions\" 1)");
+  if (m < 0) throw sme::Error(SME_EINVAL, "phrase query: m must be >= 0");
+  if (order != 0 && order != 1) throw sme::Error(SME_EINVAL, "phrase query: order must be 0 (docno) or 1 (score)");
+  // term_ids may be NULL only in a batch without a term (sme::query_phrase
+  // validates the offsets themselves before anything is read through them)
+  if (np > 0 && p_offsets[np] != 0 && !term_ids) throw sme::Error(SME_EINVAL, "bad argument");
+}
+
+int sme_query_phrase_device(sme_index *ix, const int32_t *term_ids, const int64_t *p_offsets, int np, int order, int m,
+                            void *stream, const int64_t **d_res_off, const int32_t **d_docno, const int32_t **d_freq,
+                            const double **d_score, int64_t *total) {
+  return guard([&] {
+    if (!d_res_off || !d_docno || !d_freq || !d_score) throw sme::Error(SME_EINVAL, "null argument");
+    need_phrase_args(ix, term_ids, p_offsets, np, order, m);
+    set_device(ix->ctx);
+    sme::query_phrase(ix, term_ids, p_offsets, np, order, m, stream_of(ix->ctx, stream));
+    *d_res_off = (const int64_t *)ix->d_pq_off.p;
+    *d_docno = (const int32_t *)ix->d_pq_docno.p;
+    *d_freq = (const int32_t *)ix->d_pq_freq.p;
+    *d_score = (const double *)ix->d_pq_score.p;
+    if (total) *total = ix->pq_total;
+  });
+}
+
+int sme_query_phrase(sme_index *ix, const int32_t *term_ids, const int64_t *p_offsets, int np, int order, int m,
+                     const int64_t **res_off, const int32_t **docno, const int32_t **freq, const double **score) {
+  return guard([&] {
+    if (!res_off || !docno || !freq || !score) throw sme::Error(SME_EINVAL, "null argument");
+    need_phrase_args(ix, term_ids, p_offsets, np, order, m);
+    set_device(ix->ctx);
+    hipStream_t st = ix->ctx->own_stream;
+    sme::query_phrase(ix, term_ids, p_offsets, np, order, m, st);
+    const size_t tot = (size_t)ix->pq_total;
+    ix->h_pq_off.resize((size_t)np + 1);
+    ix->h_pq_docno.resize(tot + 1);  // (never an empty vector: data() stays a valid pointer)
+    ix->h_pq_freq.resize(tot + 1);
+    ix->h_pq_score.resize(tot + 1);
+    SME_HIP(hipMemcpyAsync(ix->h_pq_off.data(), ix->d_pq_off.p, ((size_t)np + 1) * sizeof(int64_t),
+                           hipMemcpyDeviceToHost, st));
+    if (tot) {
+      SME_HIP(hipMemcpyAsync(ix->h_pq_docno.data(), ix->d_pq_docno.p, tot * sizeof(int32_t), hipMemcpyDeviceToHost,
+                             st));
+      SME_HIP(hipMemcpyAsync(ix->h_pq_freq.data(), ix->d_pq_freq.p, tot * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+      SME_HIP(hipMemcpyAsync(ix->h_pq_score.data(), ix->d_pq_score.p, tot * sizeof(double), hipMemcpyDeviceToHost,
+                             st));
+    }
+    SME_HIP(hipStreamSynchronize(st));
+    *res_off = ix->h_pq_off.data();
+    *docno = ix->h_pq_docno.data();
+    *freq = ix->h_pq_freq.data();
+    *score = ix->h_pq_score.data();
+  });
+}
+
+int sme_query_phrase_stats(const sme_index *ix, uint64_t *candidates, uint64_t *verified, uint64_t *matches) {
+  return guard([&] {
+    if (!ix || !candidates || !verified || !matches) throw sme::Error(SME_EINVAL, "null argument");
+    *candidates = ix->pq_cands;
+    *verified = ix->pq_verified;
+    *matches = ix->pq_matches;
+  });
+}
+
+int sme_index_positions(const sme_index *ix, uint64_t *records, uint64_t *positions, uint64_t *bytes) {
+  return guard([&] {
+    if (!ix || !records || !positions || !bytes) throw sme::Error(SME_EINVAL, "null argument");
+    *records = *positions = *bytes = 0;
+    if (!ix->has_positions) return;
+    *records = (uint64_t)ix->ps_records;
+    *positions = (uint64_t)ix->ps_terms;
+    *bytes = (uint64_t)(ix->ps_records + 1) * sizeof(int64_t) + (uint64_t)ix->ps_terms * sizeof(int32_t) +
+             (uint64_t)ix->ps_records * sizeof(int32_t);
   });
 }
 

@@ -3070,6 +3070,22 @@ __global__ __launch_bounds__(kAggNT) void k_twrite(AggIn in, int64_t nR, const i
   }
 }
 
+// "positions": the stream of a K6b split build holds term codes (word ranks,
+// kDocCode | docid index) -> merged ids, as k_code_to_merged turns the raw slots
+// (no v >= 0 guard as there: k_twrite writes term codes only -- a raw token without
+// a term gives no stream word -- so no stream word is negative)
+__global__ void k_stream_to_merged(int32_t *tstream, int64_t M, const int64_t *wrank, const int64_t *drank) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < M; i += (int64_t)gridDim.x * blockDim.x) {
+    const int32_t v = tstream[i];
+    tstream[i] = (int32_t)((v & kDocCode) ? drank[v & ~kDocCode] : wrank[v]);
+  }
+}
+// the docno of every stream record (docno order i)
+__global__ void k_stream_docno(const int64_t *perm, const int32_t *docno, int64_t nR, int32_t *out) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < nR; i += (int64_t)gridDim.x * blockDim.x)
+    out[i] = docno[perm[i]];
+}
+
 __device__ __forceinline__ uint64_t gram_key(const int32_t *ts, int K, int tb) {
   uint64_t k = 0;
   for (int j = 0; j < K; j++) k = (k << tb) | (uint64_t)(uint32_t)ts[j];
@@ -4533,6 +4549,39 @@ vocab_again:  // (a docid term equal to a word term: the general path, from here
   }
   prof.mark("aggregate");
 
+  // ---------------- positions (opt-in): keep the records' term streams ----------------
+  // The stream K >= 2 builds its grams from, written for a K = 1 index into
+  // buffers the index owns: record i of the docno order holds its term ids in
+  // token order.  After the aggregation, so that what the raw slots hold is
+  // settled: merged ids, or -- the K6b split still on -- codes, converted here.
+  if (K == 1 && cx->opt_positions) {
+    DevBuf tcb;
+    tcb.pool = &cx->pool;
+    const unsigned g_grid = (unsigned)std::min<int64_t>(std::max<int64_t>((nR + 3) / 4, 1), 8192);
+    int64_t *tcnt = tcb.as<int64_t>(nR + 1), *toff = ix->d_ps_off.as<int64_t>(nR + 1);
+    if (nR > 0) hipLaunchKernelGGL(k_tcount, dim3(g_grid), dim3(kAggNT), 0, st, ai, nR, tcnt);
+    SME_HIP(hipMemsetAsync(tcnt + nR, 0, sizeof(int64_t), st));
+    excl_scan(tcnt, toff, (int64_t)(nR + 1), cx->ws[23], st);
+    const int64_t M = d2h(toff + nR, st);
+    if (M >= (int64_t(1) << 31)) throw Error(SME_ELIMIT, "positions: 2^31 or more term positions");
+    int32_t *tstream = ix->d_ps_terms.as<int32_t>(M + 1);
+    int32_t *pdn = ix->d_ps_docno.as<int32_t>(nR + 1);
+    if (nR > 0) {
+      hipLaunchKernelGGL(k_twrite, dim3(g_grid), dim3(kAggNT), 0, st, ai, nR, toff, tstream);
+      if (dsplit && M > 0)
+        hipLaunchKernelGGL(k_stream_to_merged, dim3(grid_for(M)), dim3(256), 0, st, tstream, M,
+                           (const int64_t *)wrank_all, (const int64_t *)drank);
+      hipLaunchKernelGGL(k_stream_docno, dim3(grid_for(nR)), dim3(256), 0, st, (const int64_t *)perm,
+                         (const int32_t *)docno, nR, pdn);
+    }
+    SME_CHECK_LAUNCH();
+    SME_HIP(hipStreamSynchronize(st));  // tcb goes back to the pool
+    ix->ps_records = nR;
+    ix->ps_terms = M;
+    ix->has_positions = true;
+    prof.mark("positions");
+  }
+
   // ---------------- K6 sort by term ----------------
   // K6b: the docid pairs (one per record at most, docno order) as a list sorted by
   // docid index j, and every word's (shift, merged id)
@@ -4699,11 +4748,12 @@ vocab_again:  // (a docid term equal to a word term: the general path, from here
     double *d_lut = ix->d_lut.as<double>(max_tf + 1);
     SME_HIP(hipMemcpyAsync(d_lut, lut.data(), lut.size() * sizeof(double), hipMemcpyHostToDevice, st));
     const int64_t Nn = std::max<int64_t>(nR, 0);
-    double idf_ref = log10((double)(Nn / 1));  // stored df of every real term is 1 (T1)
+    ix->idf_N = Nn;
+    double idf_ref = idf_value(Nn, 1);  // stored df of every real term is 1 (T1)
     int64_t sdf = (int64_t)std::sqrt((double)std::max<int64_t>(Nn, 1)) + 1;
     std::vector<double> by_df(sdf + 1), by_q(Nn / std::max<int64_t>(sdf, 1) + 2);
-    for (int64_t d = 1; d <= sdf; d++) by_df[d] = log10((double)(Nn / d));
-    for (size_t q = 0; q < by_q.size(); q++) by_q[q] = log10((double)q);
+    for (int64_t d = 1; d <= sdf; d++) by_df[d] = idf_value(Nn, d);
+    for (size_t q = 0; q < by_q.size(); q++) by_q[q] = idf_value((int64_t)q, 1);
     double *d_bydf = W[W_U16].as<double>(by_df.size() + by_q.size());
     double *d_byq = d_bydf + by_df.size();
     SME_HIP(hipMemcpyAsync(d_bydf, by_df.data(), by_df.size() * sizeof(double), hipMemcpyHostToDevice, st));
@@ -4868,11 +4918,12 @@ void reweight_index(sme_index *ix, int64_t N, const int64_t *d_gdf, hipStream_t 
   std::vector<double> lut(ix->max_tf + 1, 0.0);
   for (int i = 1; i <= ix->max_tf; i++) lut[i] = 1.0 + log((double)i);
   const int64_t Nn = std::max<int64_t>(N, 0);
-  double idf_ref = log10((double)(Nn / 1));
+  ix->idf_N = Nn;
+  double idf_ref = idf_value(Nn, 1);
   int64_t sdf = (int64_t)std::sqrt((double)std::max<int64_t>(Nn, 1)) + 1;
   std::vector<double> by_df(sdf + 1), by_q(Nn / std::max<int64_t>(sdf, 1) + 2);
-  for (int64_t d = 1; d <= sdf; d++) by_df[d] = log10((double)(Nn / d));
-  for (size_t q = 0; q < by_q.size(); q++) by_q[q] = log10((double)q);
+  for (int64_t d = 1; d <= sdf; d++) by_df[d] = idf_value(Nn, d);
+  for (size_t q = 0; q < by_q.size(); q++) by_q[q] = idf_value((int64_t)q, 1);
   double *d_lut = ix->d_lut.as<double>(lut.size());
   double *d_tab = W[57].as<double>(by_df.size() + by_q.size());
   SME_HIP(hipMemcpyAsync(d_lut, lut.data(), lut.size() * sizeof(double), hipMemcpyHostToDevice, st));

@@ -1,6 +1,7 @@
 // sme_internal.hpp -- context and index objects behind the C-ABI.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
 
 #include <memory>
@@ -71,6 +72,7 @@ struct sme_ctx {
   int64_t opt_fuzzy_scan = 0;      // "fuzzy_scan": 1 = every suggestion word takes the whole vocabulary as candidates
   int64_t opt_bool_chunk = 1024;  // "bool_chunk": Boolean-query candidates per workgroup (64..4096, multiples of 64)
   int64_t opt_bool_driver = 0;    // "bool_driver": 0 = the required group with the fewest postings drives, 1 = the first
+  int64_t opt_positions = 0;      // "positions": 1 = a K = 1 build keeps every record's term stream (phrase queries)
   int64_t opt_corpus_keep = int64_t(16) << 30;  // "corpus_keep_bytes": host-corpus builds keep their device copy
                                                 // (no hipMalloc next build) only up to this size
   // pinned host staging of device -> host record copies into pageable caller
@@ -186,6 +188,26 @@ struct sme_index {
   std::vector<int64_t> h_bq_off;
   std::vector<int32_t> h_bq_docno;
   std::vector<double> h_bq_score;
+  // positions (a K = 1 build with the "positions" option; sme_phrase.hip): the
+  // records' term streams in docno-ascending record order -- a forward index.
+  // Empty buffers (ps_records == 0 and nothing allocated) when the index keeps none.
+  sme::DevBuf d_ps_off;    // int64 [ps_records + 1]  stream offsets
+  sme::DevBuf d_ps_terms;  // int32 [ps_terms]        term ids in token order
+  sme::DevBuf d_ps_docno;  // int32 [ps_records]      docno of each stream record, ascending
+  int64_t ps_records = 0, ps_terms = 0;
+  bool has_positions = false;
+  int64_t idf_N = 0;  // the N the weights were last computed with (build, sme_index_reweight)
+  // phrase queries: the last call's outputs (owned by the index until the next
+  // one; its temporaries are pooled blocks of the call) and what it counted
+  sme::DevBuf d_pq_off;    // int64 [np + 1]  result offsets
+  sme::DevBuf d_pq_docno;  // int32 [total]   matching documents
+  sme::DevBuf d_pq_freq;   // int32 [total]   occurrences of the phrase in each
+  sme::DevBuf d_pq_score;  // double [total]  their scores
+  int64_t pq_total = 0;
+  uint64_t pq_cands = 0, pq_verified = 0, pq_matches = 0;  // driver postings; filter survivors; matches before the cut
+  std::vector<int64_t> h_pq_off;
+  std::vector<int32_t> h_pq_docno, h_pq_freq;
+  std::vector<double> h_pq_score;
   // stage timings of the build that produced this index (ms)
   std::vector<std::pair<std::string, float>> profile;
   ~sme_index() { ctx->live_indexes--; }  // members (pooled buffers) are released after this body
@@ -194,7 +216,8 @@ struct sme_index {
     for (sme::DevBuf *b : {&d_term_off, &d_term_chars, &d_off, &d_docno_d, &d_tf_d, &d_w, &d_idf, &d_lut, &d_gram, &d_docno_o,
                            &d_tf_o, &d_rec_docno, &d_rec_first, &d_ser, &d_hrow_of, &d_heavy, &d_spk, &d_wkeys, &d_wgoff,
                            &d_wgterm, &d_wx_off, &d_wx_ids, &d_wx_in, &d_wx_plan, &d_wx_choff, &d_wx_moff, &d_wx_scan, &d_fz_off,
-                           &d_fz_ids, &d_fz_dist, &d_bq_off, &d_bq_docno, &d_bq_score})
+                           &d_fz_ids, &d_fz_dist, &d_bq_off, &d_bq_docno, &d_bq_score, &d_ps_off, &d_ps_terms, &d_ps_docno,
+                           &d_pq_off, &d_pq_docno, &d_pq_freq, &d_pq_score})
       b->pool = &c->pool;
   }
 };
@@ -353,4 +376,17 @@ void suggest_terms(sme_index *ix, const uint8_t *words, const int64_t *offs, int
 // d_bq_docno / d_bq_score / bq_total, and the call's counts bq_cands / bq_matches
 void query_boolean(sme_index *ix, const int32_t *term_ids, const int64_t *g_offsets, const uint8_t *g_flags,
                    const int64_t *q_offsets, int nq, int order, int m, hipStream_t st);
+// phrase queries (sme_phrase.hip): np phrases of term ids (host arrays, validated
+// here) over the positions a K = 1 build kept -> per phrase the matching documents
+// with the phrase's frequency and score, ordered (0 docno asc, 1 score desc then
+// docno asc) and cut to m: ix->d_pq_off / d_pq_docno / d_pq_freq / d_pq_score /
+// pq_total, and the call's counts pq_cands / pq_verified / pq_matches
+void query_phrase(sme_index *ix, const int32_t *term_ids, const int64_t *p_offsets, int np, int order, int m,
+                  hipStream_t st);
+// The idf of a term with document frequency df among N documents, the one
+// expression behind the build's idf tables (idf_by_df[df] = idf_value(N, df),
+// idf_by_q[q] = idf_value(q, 1) read at q = N / df: log10 of the integer quotient)
+// and a phrase's score.  Host only: the
+// tables exist because the platform libm's log10 is the reference's.
+inline double idf_value(int64_t N, int64_t df) { return log10((double)(N / df)); }
 }  // namespace sme
