@@ -3234,352 +3234,7 @@ __global__ void k_gram_comp_rep(const uint32_t *rep, int64_t Vg, int K, const in
     for (int c = 0; c < K; c++) gcomp[g * K + c] = tstream[(int64_t)rep[g] + c];
 }
 
-// ============================================================================
-// K8: reducer output order -- per term, a STABLE sort by tf descending of the
-// docno-ascending postings (MyReducer.reduce's Collections.sort over
-// PostingWritable.compareTo, TermKGramDocIndexer.java:211, PostingWritable.java:57-59).
-// Segmented counting sort: the term CSR already delimits the segments and tf is a
-// small integer, so one read + one write per posting replaces a full radix sort.
-// ============================================================================
-constexpr int kTfTiny = 8;      // segments up to this: one thread each (insertion sort in registers)
-constexpr int kTfSmall = 64;    // segments up to one wave chunk: rank by lane compares
-constexpr int kTfWave = 512;    // up to this: one-wave blocks (no cross-wave barriers)
-constexpr int kTfMedium = 8192; // up to this: 4-wave blocks; beyond: tiles
-constexpr int kTfSortMaxTf = 1023;  // LDS counters (max_tf + 1) x 16 x 4 B <= 64 KiB; above: radix sort
-
-// segments of length <= kTfTiny (every docid term, most rare words): one thread
-// each, a stable insertion sort by tf desc in registers
-__global__ __launch_bounds__(256) void k_tfsort_tiny(const int64_t *__restrict__ off, int64_t V,
-                                                     const int32_t *__restrict__ docno_d,
-                                                     const int32_t *__restrict__ tf_d, int32_t *docno_o,
-                                                     int32_t *tf_o) {
-  for (int64_t s = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; s < V; s += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t b = off[s];
-    const int n = (int)(off[s + 1] - b);
-    if (n > kTfTiny || n == 0) continue;
-    int32_t t[kTfTiny], d[kTfTiny];
-#pragma unroll
-    for (int j = 0; j < kTfTiny; j++) {
-      t[j] = j < n ? tf_d[b + j] : INT_MIN;  // INT_MIN: padding sinks to the end
-      d[j] = j < n ? docno_d[b + j] : 0;
-    }
-#pragma unroll
-    for (int j = 1; j < kTfTiny; j++) {  // stable: an item passes only strictly smaller tfs
-#pragma unroll
-      for (int k = j; k > 0; k--) {
-        if (t[k - 1] < t[k]) {
-          const int32_t x = t[k - 1], y = d[k - 1];
-          t[k - 1] = t[k];
-          d[k - 1] = d[k];
-          t[k] = x;
-          d[k] = y;
-        }
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < kTfTiny; j++)
-      if (j < n) {
-        docno_o[b + j] = d[j];
-        tf_o[b + j] = t[j];
-      }
-  }
-}
-
-// segments of length in (kTfTiny, kTfSmall] (from a class list): one wave each;
-// output rank of lane i = #{j : tf_j > tf_i} + #{j < i : tf_j == tf_i}
-__global__ __launch_bounds__(256) void k_tfsort_small(const int64_t *__restrict__ off,
-                                                      const int32_t *__restrict__ seg,
-                                                      const unsigned long long *__restrict__ nseg,
-                                                      const int32_t *__restrict__ docno_d,
-                                                      const int32_t *__restrict__ tf_d, int32_t *docno_o,
-                                                      int32_t *tf_o) {
-  const int lane = threadIdx.x & 63;
-  const int64_t nw = (int64_t)gridDim.x * (blockDim.x >> 6), ns = (int64_t)*nseg;
-  for (int64_t q = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); q < ns; q += nw) {
-    const int64_t s = seg[q];
-    const int64_t b = off[s];
-    const int n = (int)(off[s + 1] - b);
-    const bool v = lane < n;
-    const int32_t t = v ? tf_d[b + lane] : 0, d = v ? docno_d[b + lane] : 0;
-    int r = 0;
-    for (int j = 0; j < n; j++) {
-      const int32_t tj = __shfl(t, j, 64);
-      r += (tj > t) || (tj == t && j < lane);
-    }
-    if (v) {
-      docno_o[b + r] = d;
-      tf_o[b + r] = t;
-    }
-  }
-}
-
-// one NW-wave block per segment (length in (lo, hi]): wave w owns a contiguous run
-// of 64-posting chunks.  Pass 1 counts tf per wave, a block scan orders the
-// counters as (tf desc, wave asc), pass 2 places every posting at its counter +
-// its rank among equal-tf lanes of the chunk (ballot), which keeps docno order.
-template <int NW>
-__global__ __launch_bounds__(NW * 64) void k_tfsort_block(const int64_t *__restrict__ off, int64_t V,
-                                                          const int32_t *__restrict__ docno_d,
-                                                          const int32_t *__restrict__ tf_d, int32_t *docno_o,
-                                                          int32_t *tf_o, const int32_t *__restrict__ seg,
-                                                          const unsigned long long *__restrict__ nseg, int max_tf) {
-  extern __shared__ int32_t cnt[];  // [(max_tf - tf) * NW + w]
-  __shared__ int32_t wsum[NW];
-  constexpr int NT = NW * 64;
-  const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
-  const int L = (max_tf + 1) * NW;
-  const uint64_t lt_mask = (1ull << lane) - 1;
-  const int64_t ns = (int64_t)*nseg;
-  for (int64_t q = blockIdx.x; q < ns; q += gridDim.x) {
-    const int64_t s = seg[q];
-    const int64_t b = off[s], n = off[s + 1] - b;
-    for (int j = tid; j < L; j += NT) cnt[j] = 0;
-    __syncthreads();
-    const int64_t nch = (n + 63) >> 6, cpw = (nch + NW - 1) / NW;
-    const int64_t c0 = (int64_t)w * cpw, c1 = c0 + cpw < nch ? c0 + cpw : nch;
-    int32_t tn = c0 < c1 && (c0 << 6) + lane < n ? tf_d[b + (c0 << 6) + lane] : -1;  // one chunk ahead
-    for (int64_t c = c0; c < c1; c++) {
-      const int64_t i = (c << 6) + lane;
-      const bool v = i < n;
-      const int32_t t = tn;
-      tn = c + 1 < c1 && i + 64 < n ? tf_d[b + i + 64] : -1;
-      uint64_t pend = __ballot(v);
-      while (pend) {
-        const int32_t tv = __shfl(t, __ffsll((unsigned long long)pend) - 1, 64);
-        const uint64_t m = __ballot(t == tv);
-        if (lane == 0) cnt[(max_tf - tv) * NW + w] += __popcll(m);
-        pend &= ~m;
-      }
-    }
-    __syncthreads();
-    // exclusive scan of cnt[0..L) (each thread a contiguous run, then across threads)
-    const int per = (L + NT - 1) / NT, j0 = tid * per, j1 = j0 + per < L ? j0 + per : L;
-    int run = 0;
-    for (int j = j0; j < j1; j++) run += cnt[j];
-    int inc = run;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int u = __shfl_up(inc, o, 64);
-      if (lane >= o) inc += u;
-    }
-    if (lane == 63) wsum[w] = inc;
-    __syncthreads();
-    int base = inc - run;
-    for (int k = 0; k < w; k++) base += wsum[k];
-    for (int j = j0; j < j1; j++) {
-      const int c = cnt[j];
-      cnt[j] = base;
-      base += c;
-    }
-    __syncthreads();
-    int32_t tn2 = -1, dn2 = 0;  // one chunk ahead
-    if (c0 < c1 && (c0 << 6) + lane < n) {
-      tn2 = tf_d[b + (c0 << 6) + lane];
-      dn2 = docno_d[b + (c0 << 6) + lane];
-    }
-    for (int64_t c = c0; c < c1; c++) {
-      const int64_t i = (c << 6) + lane;
-      const bool v = i < n;
-      const int32_t t = tn2, d = dn2;
-      if (c + 1 < c1 && i + 64 < n) {
-        tn2 = tf_d[b + i + 64];
-        dn2 = docno_d[b + i + 64];
-      } else {
-        tn2 = -1;
-      }
-      uint64_t pend = __ballot(v);
-      while (pend) {
-        const int32_t tv = __shfl(t, __ffsll((unsigned long long)pend) - 1, 64);
-        const uint64_t m = __ballot(t == tv);
-        const int slot = (max_tf - tv) * NW + w;
-        const int cb = cnt[slot];
-        if (t == tv) {
-          const int64_t p = b + cb + __popcll(m & lt_mask);
-          docno_o[p] = d;
-          tf_o[p] = t;
-        }
-        if (lane == 0) cnt[slot] = cb + __popcll(m);
-        pend &= ~m;
-      }
-    }
-    __syncthreads();
-  }
-}
-
-// Segments longer than kTfMedium are cut into tiles of kTfTile postings so that a
-// 1M-posting term spreads over many CUs: (1) per tile tf counts, (2) per segment
-// an exclusive scan of the counts in (tf desc, tile asc) order, (3) per tile the
-// ballot placement of k_tfsort_block from the tile's scanned counters.
-constexpr int kTfTile = 4096;
-
-// segment lists by class (medium: 4-wave blocks, large: tiles), appended with
-// one global atomic per block and list; list order is free (segments are
-// independent and their output ranges fixed)
-__global__ __launch_bounds__(256) void k_tf_classify(const int64_t *__restrict__ off, int64_t V, int32_t *med,
-                                                     int32_t *large, int32_t *small, int32_t *wave,
-                                                     unsigned long long *ctr) {
-  __shared__ unsigned int s_n[4];
-  __shared__ unsigned long long s_b[4];
-  for (int64_t s0 = (int64_t)blockIdx.x * 256; s0 < V; s0 += (int64_t)gridDim.x * 256) {  // block-uniform
-    const int64_t s = s0 + threadIdx.x;
-    const int64_t n = s < V ? off[s + 1] - off[s] : 0;
-    const int cls = n > kTfMedium ? 1 : n > kTfWave ? 0 : n > kTfSmall ? 3 : n > kTfTiny ? 2 : -1;  // ctr index
-    if (threadIdx.x < 4) s_n[threadIdx.x] = 0;
-    __syncthreads();
-    unsigned int pos = 0;
-    if (cls >= 0) pos = atomicAdd(&s_n[cls], 1u);
-    __syncthreads();
-    if (threadIdx.x < 4)
-      s_b[threadIdx.x] = s_n[threadIdx.x] ? atomicAdd(&ctr[threadIdx.x], (unsigned long long)s_n[threadIdx.x]) : 0ull;
-    __syncthreads();
-    if (cls == 0) med[s_b[0] + pos] = (int32_t)s;
-    if (cls == 1) large[s_b[1] + pos] = (int32_t)s;
-    if (cls == 2) small[s_b[2] + pos] = (int32_t)s;
-    if (cls == 3) wave[s_b[3] + pos] = (int32_t)s;
-    __syncthreads();
-  }
-}
-// tiles of large segment q (0 beyond the list: the scan covers V + 1 entries)
-__global__ void k_tf_ntiles(const int64_t *off, const int32_t *large, const unsigned long long *nlarge, int64_t V,
-                            int64_t *nt) {
-  const int64_t nl = (int64_t)*nlarge;
-  for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q <= V; q += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t n = q < nl ? off[large[q] + 1] - off[large[q]] : 0;
-    nt[q] = (n + kTfTile - 1) / kTfTile;
-  }
-}
-
-// segment of tile tau: the s with toff[s] <= tau < toff[s + 1]
-__device__ __forceinline__ int64_t tile_segment(const int64_t *toff, int64_t V, int64_t tau) {
-  int64_t lo = 0, hi = V;  // toff[lo] <= tau < toff[hi]
-  while (hi - lo > 1) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (toff[mid] <= tau) lo = mid;
-    else hi = mid;
-  }
-  return lo;
-}
-
-// (1) one wave per tile: LDS counts (order-free), written as tcnt[tau][max_tf - tf]
-__global__ __launch_bounds__(256) void k_tf_tile_count(const int64_t *__restrict__ off,
-                                                       const int32_t *__restrict__ large,
-                                                       const unsigned long long *__restrict__ nlarge,
-                                                       const int64_t *__restrict__ toff, int64_t ntiles,
-                                                       const int32_t *__restrict__ tf_d, int max_tf,
-                                                       int32_t *tcnt) {
-  extern __shared__ int32_t h[];  // 4 waves x (max_tf + 1)
-  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, F = max_tf + 1;
-  int32_t *hw = h + w * F;
-  const int64_t nwv = (int64_t)gridDim.x * 4;
-  const int64_t nl = (int64_t)*nlarge;
-  for (int64_t tau = (int64_t)blockIdx.x * 4 + w; tau < ntiles; tau += nwv) {  // wave-uniform
-    const int64_t q = tile_segment(toff, nl, tau), s = large[q];
-    const int64_t b = off[s] + (tau - toff[q]) * kTfTile, e = min(off[s + 1], b + (int64_t)kTfTile);
-    for (int j = lane; j < F; j += 64) hw[j] = 0;
-    __builtin_amdgcn_wave_barrier();
-    // per 64-posting chunk: one LDS add per distinct tf (ballot groups) -- most
-    // postings have tf 1, and per-lane atomics on that one counter serialise
-    int32_t tn = b + lane < e ? tf_d[b + lane] : -1;  // the next chunk loads before this one is counted
-    for (int64_t c = b; c < e; c += 64) {
-      const bool v = c + lane < e;
-      const int32_t t = tn;
-      tn = c + 64 + lane < e ? tf_d[c + 64 + lane] : -1;
-      uint64_t pend = __ballot(v);
-      while (pend) {
-        const int32_t tv = __shfl(t, __ffsll((unsigned long long)pend) - 1, 64);
-        const uint64_t m = __ballot(t == tv);
-        if (lane == 0) hw[max_tf - tv] += __popcll(m);
-        pend &= ~m;
-      }
-    }
-    __builtin_amdgcn_wave_barrier();
-    for (int j = lane; j < F; j += 64) tcnt[tau * F + j] = hw[j];
-    __builtin_amdgcn_wave_barrier();
-  }
-}
-
-// (2) one block per large segment: counters -> segment-relative start positions,
-// in (tf desc, tile asc) order.  Thread f owns counter column f (= max_tf - tf,
-// up to 4 per thread): its total over the segment's tiles, one block scan of the
-// totals, then a walk down its column (coalesced across threads at every tile).
-__global__ __launch_bounds__(256) void k_tf_tile_scan(const unsigned long long *__restrict__ nlarge,
-                                                      const int64_t *__restrict__ toff, int max_tf, int32_t *tcnt) {
-  __shared__ int32_t sc[256 / 64 + 1];
-  const int tid = threadIdx.x, F = max_tf + 1;
-  const int64_t nl = (int64_t)*nlarge;
-  for (int64_t q = blockIdx.x; q < nl; q += gridDim.x) {
-    const int64_t t0 = toff[q], T = toff[q + 1] - t0;
-    int32_t *c = tcnt + t0 * F;
-    int32_t carry = 0;
-    for (int f0 = 0; f0 < F; f0 += 256) {  // block-uniform
-      const int f = f0 + tid;
-      int32_t tot = 0;
-      if (f < F) {
-#pragma unroll 8
-        for (int64_t j = 0; j < T; j++) tot += c[j * F + f];
-      }
-      int32_t all;
-      int32_t run = carry + block_excl_sum<256, int32_t>(tot, sc, &all);
-      carry += all;
-      if (f < F) {
-#pragma unroll 8
-        for (int64_t j = 0; j < T; j++) {
-          const int32_t x = c[j * F + f];
-          c[j * F + f] = run;
-          run += x;
-        }
-      }
-    }
-  }
-}
-
-// (3) one wave per tile: stable placement from the tile's counters
-__global__ __launch_bounds__(256) void k_tf_tile_place(const int64_t *__restrict__ off,
-                                                       const int32_t *__restrict__ large,
-                                                       const unsigned long long *__restrict__ nlarge,
-                                                       const int64_t *__restrict__ toff, int64_t ntiles,
-                                                       const int32_t *__restrict__ docno_d,
-                                                       const int32_t *__restrict__ tf_d, int max_tf,
-                                                       const int32_t *__restrict__ tcnt, int32_t *docno_o,
-                                                       int32_t *tf_o) {
-  extern __shared__ int32_t h[];
-  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, F = max_tf + 1;
-  int32_t *hw = h + w * F;
-  const uint64_t lt_mask = (1ull << lane) - 1;
-  const int64_t nwv = (int64_t)gridDim.x * 4;
-  const int64_t nl = (int64_t)*nlarge;
-  for (int64_t tau = (int64_t)blockIdx.x * 4 + w; tau < ntiles; tau += nwv) {
-    const int64_t q = tile_segment(toff, nl, tau), s = large[q];
-    const int64_t sb = off[s];
-    const int64_t b = sb + (tau - toff[q]) * kTfTile, e = min(off[s + 1], b + (int64_t)kTfTile);
-    for (int j = lane; j < F; j += 64) hw[j] = tcnt[tau * F + j];
-    __builtin_amdgcn_wave_barrier();
-    // the next chunk's (tf, docno) are loaded before this chunk's placement
-    int32_t tn = b + lane < e ? tf_d[b + lane] : -1, dnx = b + lane < e ? docno_d[b + lane] : 0;
-    for (int64_t c = b; c < e; c += 64) {
-      const bool v = c + lane < e;
-      const int32_t t = tn, d = dnx;
-      const int64_t in = c + 64 + lane;
-      tn = in < e ? tf_d[in] : -1;
-      dnx = in < e ? docno_d[in] : 0;
-      uint64_t pend = __ballot(v);
-      while (pend) {
-        const int32_t tv = __shfl(t, __ffsll((unsigned long long)pend) - 1, 64);
-        const uint64_t m = __ballot(t == tv);
-        const int slot = max_tf - tv;
-        const int cb = hw[slot];
-        if (t == tv) {
-          const int64_t p = sb + cb + __popcll(m & lt_mask);
-          docno_o[p] = d;
-          tf_o[p] = t;
-        }
-        if (lane == 0) hw[slot] = cb + __popcll(m);
-        pend &= ~m;
-      }
-    }
-    __builtin_amdgcn_wave_barrier();
-  }
-}
+// (K8, the reducer output order, is sme_tfsort.hip: tf_sort_segments)
 
 // ============================================================================
 // host orchestration
@@ -4774,62 +4429,12 @@ vocab_again:  // (a docid term equal to a word term: the general path, from here
   // ---------------- K8 reduce-output order ----------------
   int32_t *docno_o = ix->d_docno_o.as<int32_t>(PP + 1), *tf_o = ix->d_tf_o.as<int32_t>(PP + 1);
   if (PP > 0 && max_tf <= kTfSortMaxTf) {
-    // segmented counting sort over the term CSR (no full-width key sort)
-    hipLaunchKernelGGL(k_tfsort_tiny, dim3(grid_for(Vi)), dim3(256), 0, st, off, Vi, docno_d, tf_d, docno_o, tf_o);
-    // medium and large segments as lists (a grid-stride walk over all V terms costs a
-    // dependent offset load per term and block)
-    int64_t *ntl = W[W_FKEYS].as<int64_t>(3 * (Vi + 1)), *toff = W[W_FREPS].as<int64_t>(Vi + 1);
-    int32_t *seg_med = reinterpret_cast<int32_t *>(ntl + Vi + 1), *seg_large = seg_med + Vi,
-            *seg_small = seg_large + Vi, *seg_wave = seg_small + Vi;
-    unsigned long long *nseg = cnt + 28;  // [0] medium, [1] large, [2] small, [3] wave-sized
-    SME_HIP(hipMemsetAsync(nseg, 0, 4 * sizeof(unsigned long long), st));
-    hipLaunchKernelGGL(k_tf_classify, dim3(grid_for(Vi)), dim3(256), 0, st, off, Vi, seg_med, seg_large, seg_small,
-                       seg_wave, nseg);
-    // the small / medium / wave-sized classes (disjoint terms, disjoint output
-    // ranges) run on the auxiliary stream beside the large tiles' count / scan /
-    // place chain, which also waits on a host read of the tile count (tf sort
-    // 3.1 -> 2.8 ms; k_docno beside the tokenizer, tried the same way, slowed the
-    // tokenizer by more than it saved)
-    hipStream_t s2 = cx->aux_stream;
-    SME_HIP(hipEventRecord(cx->ev_fork, st));
-    SME_HIP(hipStreamWaitEvent(s2, cx->ev_fork, 0));
-    // every exit from this block -- a throw between the fork and the join
-    // included -- makes st wait for the auxiliary stream's kernels, so they never
-    // write docno_o / tf_o after the build's workspace is released or reused
-    struct AuxJoin {
-      hipStream_t st, s2;
-      hipEvent_t ev;
-      ~AuxJoin() {
-        (void)hipEventRecord(ev, s2);
-        (void)hipStreamWaitEvent(st, ev, 0);
-      }
-    } aux_join{st, s2, cx->ev_join};
-    hipLaunchKernelGGL(k_tfsort_small, dim3(grid_for(Vi * 64, 256, 8192)), dim3(256), 0, s2, off, seg_small, nseg + 2,
-                       docno_d, tf_d, docno_o, tf_o);
-    const size_t lds4 = (size_t)(max_tf + 1) * 4 * sizeof(int32_t);
-    hipLaunchKernelGGL(k_tfsort_block<4>, dim3((unsigned)std::min<int64_t>(std::max<int64_t>(Vi, 1), 4096)),
-                       dim3(256), lds4, s2, off, Vi, docno_d, tf_d, docno_o, tf_o, seg_med, nseg, max_tf);
-    hipLaunchKernelGGL(k_tfsort_block<1>, dim3((unsigned)std::min<int64_t>(std::max<int64_t>(Vi, 1), 32768)),
-                       dim3(64), lds4 / 4, s2, off, Vi, docno_d, tf_d, docno_o, tf_o, seg_wave, nseg + 3, max_tf);
-    SME_CHECK_LAUNCH();
-    // large segments: tiles spread over the whole chip
-    hipLaunchKernelGGL(k_tf_ntiles, dim3(grid_for(Vi + 1)), dim3(256), 0, st, off, seg_large, nseg + 1, Vi, ntl);
-    size_t tbb = 0;
-    excl_scan(ntl, toff, (int64_t)(Vi + 1), cx->ws[23], st);
-    const int64_t ntiles = d2h(toff + Vi, st);
-    if (ntiles > 0) {
-      const int F = max_tf + 1;
-      int32_t *tcnt = reinterpret_cast<int32_t *>(W[W_CKEY].as<uint64_t>((ntiles * F + 1) / 2 + 1));
-      const unsigned tg = (unsigned)std::min<int64_t>((ntiles + 3) / 4, 8192);
-      hipLaunchKernelGGL(k_tf_tile_count, dim3(tg), dim3(256), (size_t)4 * F * sizeof(int32_t), st, off, seg_large,
-                         nseg + 1, toff, ntiles, tf_d, max_tf, tcnt);
-      hipLaunchKernelGGL(k_tf_tile_scan, dim3((unsigned)std::min<int64_t>(Vi, 8192)), dim3(256), 0, st, nseg + 1,
-                         toff, max_tf, tcnt);
-      hipLaunchKernelGGL(k_tf_tile_place, dim3(tg), dim3(256), (size_t)4 * F * sizeof(int32_t), st, off, seg_large,
-                         nseg + 1, toff, ntiles, docno_d, tf_d, max_tf, tcnt, docno_o, tf_o);
-    }
-    SME_CHECK_LAUNCH();
-  } else if (PP > 0) {  // (aux_join: st waits for the auxiliary stream here)
+    // segmented counting sort over the term CSR (no full-width key sort); the
+    // shorter segment classes run on the auxiliary stream, and st waits for it
+    // on every exit (sme_tfsort.hip)
+    tf_sort_segments(off, Vi, PP, docno_d, tf_d, max_tf, docno_o, tf_o, W[W_FKEYS], W[W_FREPS], W[W_CKEY], cx->ws[23],
+                     cnt + 28, st, cx->aux_stream, cx->ev_fork, cx->ev_join);
+  } else if (PP > 0) {
     const int tfb = bits_for((uint64_t)max_tf);
     // (the sorted keys are merged term ids: after the K6b split they are wider than
     // the term sort's word ranks)

@@ -322,6 +322,19 @@ void reduce_max(const T *in, int64_t n, T *d_max, hipStream_t st);
 // runs of equal keys (sorted input) -> (key, sum of vals) per run, *d_runs = count
 void reduce_by_key_sum(const uint64_t *keys, const int32_t *vals, int64_t n, uint64_t *ukeys, int32_t *sums,
                        int64_t *d_runs, DevBuf &flags, DevBuf &pos, DevBuf &scan, hipStream_t st);
+// K8, the reducer's output order (sme_tfsort.hip): per segment [off[s], off[s + 1])
+// of the term CSR, s < V, P = off[V], a stable sort by tf descending of (docno_d, tf_d) into
+// (docno_o, tf_o); the inputs stay as they are.  A segmented counting sort for
+// 1 <= max_tf <= kTfSortMaxTf (every tf in 0..max_tf); tf_d is 16-byte aligned.
+// Scratch: lists (3 (V + 1) int64), tiles (V + 1 int64), tcnt (one u32 per tile of
+// 4096 postings and tf value + one per tile), scan (excl_scan's) and the four
+// device counters nseg.  The shorter segment classes run on aux_stream between
+// the two events; on every exit, a throw included, st waits for aux_stream.
+constexpr int kTfSortMaxTf = 1023;  // LDS counters (max_tf + 1) x 16 x 4 B <= 64 KiB
+void tf_sort_segments(const int64_t *off, int64_t V, int64_t P, const int32_t *docno_d, const int32_t *tf_d,
+                      int max_tf, int32_t *docno_o, int32_t *tf_o, DevBuf &lists, DevBuf &tiles, DevBuf &tcnt, DevBuf &scan,
+                      unsigned long long *nseg, hipStream_t st, hipStream_t aux_stream, hipEvent_t ev_fork,
+                      hipEvent_t ev_join);
 void serialize_index(sme_index *ix, hipStream_t st);
 // reference-layout output from doc shards (sme_merge.hip): per-owner blobs of a
 // shard's terms and postings, and the owner's merge of the received blobs
