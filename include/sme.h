@@ -482,6 +482,74 @@ int sme_query_phrase_device(sme_index *ix, const int32_t *term_ids, const int64_
                             const int32_t **d_freq, const double **d_score, int64_t *total);
 int sme_query_phrase_stats(const sme_index *ix, uint64_t *candidates, uint64_t *verified, uint64_t *matches);
 
+/* Proximity queries: "these terms near each other" (Galago's #od:N and #uw:N; no
+ * reference counterpart, a K-gram index only knows adjacency).  Query i is the term
+ * ids term_ids[q_offsets[i] .. q_offsets[i + 1]) (nq + 1 entries from 0; at most
+ * 32, sme_lookup_terms' ids, -1 = unknown), a width N = widths[i] (1 <= N <=
+ * 2^31 - 1) and a kind kinds[i]; host arrays.  Everything is evaluated inside one
+ * record's term stream (sme_index_positions): nothing crosses a record's end, and
+ * freq of a document sums over all records of its docno, as for phrases.
+ *
+ * Kind 0, the ordered window (#od:N).  For terms t_0 .. t_{L-1} define over the
+ * positions p of a record:
+ *   R_0[p]      iff stream[p] == t_0;
+ *   R_{j+1}[p]  iff stream[p] == t_{j+1} and R_j[q] for some q in [p - N, p - 1].
+ * freq = the number of positions p with R_{L-1}[p]: the distinct END positions of
+ * chains in which every next term follows the previous one by at most N
+ * positions.  This is existence over all chains, not a greedy match: in
+ * "a b b x c" with N = 2 the chain through the second b reaches c (the one through
+ * the first does not), in "a b c b" with N = 3 the chain through the first b
+ * reaches c (the one through the last does not); both match.  Repeated terms are
+ * ordinary ("a a").  N = 1 is the exact phrase with sme_query_phrase's freq (ends
+ * and starts correspond one to one); L = 1 gives the term's tf.
+ *
+ * Kind 1, the unordered window (#uw:N).  The query is the SET T of its distinct
+ * terms (a term listed twice counts once).  freq = the number of positions e with
+ * stream[e] in T and every term of T occurring in [max(0, e - N + 1), e]: the
+ * window of N positions ending at a query term holds all of them.  N < |T|
+ * matches nothing; a window is clipped at the record's start, never continued into
+ * the previous record.
+ *
+ * Both kinds: an empty query and a query holding -1 have no result.  score =
+ * (1 + ln freq) * idf(df), one fp64 product, with df = the query's matching
+ * documents BEFORE the cut and idf and N_docs exactly as sme_query_phrase uses
+ * them (log10(N / 1) in SME_IDF_REFERENCE, log10(N / df) with the integer quotient
+ * otherwise; N as of the last sme_index_reweight).  1 + ln f comes from a table
+ * kept with the index that continues the weights' own past the largest tf: an
+ * unordered freq can reach the sum of the distinct terms' tfs.  order 0: a query's
+ * results by docno ascending (signed int32 order); order 1: by score descending,
+ * then docno ascending; both then cut to the first m entries (m == 0: no cut).
+ * Query i's results are docno[] / freq[] / score[] at [res_off[i], res_off[i + 1]);
+ * nq + 1 offsets, owned by the index until the next proximity call on it (host
+ * memory from the host entry; device memory from the device entry, with *total =
+ * res_off[nq], total may be NULL).  A proximity call leaves the buffers of the
+ * last wildcard, suggestion, Boolean and phrase call alone, and the other way
+ * round.  nq == 0 is valid.
+ * Limits: more than 32 terms in a query is SME_ELIMIT, as are 2^31 or more term
+ * slots in a batch and 2^31 or more documents holding all terms of their query
+ * over a batch (before positions are looked at).  A term id outside [-1, V), a
+ * width below 1 and a kind other than 0 / 1 are SME_EINVAL; every one of these
+ * messages names the query.  q_offsets, widths and kinds are never NULL when
+ * nq > 0; term_ids may be NULL only in a batch without a term.  m < 0, an order
+ * other than 0 / 1 and offsets that do not ascend from 0 are SME_EINVAL, as is,
+ * with a message that says which: an index without positions, one with K != 1, one
+ * without a query side, a chargram output.  A freq past the scorer table (the
+ * index's tfs and its streams disagreeing) is SME_ELIMIT, never a read past it.
+ * Candidates come from the query's term with the fewest postings and are filtered
+ * as a phrase's are ("bool_chunk" cuts them); the survivors' records are scanned,
+ * every stream word read once whatever the query's length.
+ * sme_query_near_stats reports on the last proximity call on the index:
+ * *candidates = the driver postings examined, *verified = the (query, document)
+ * pairs that hold all the query's terms and had their records scanned, *matches =
+ * those with freq > 0, the matches before the cut. */
+int sme_query_near(sme_index *ix, const int32_t *term_ids, const int64_t *q_offsets, const int32_t *widths,
+                   const uint8_t *kinds, int nq, int order, int m, const int64_t **res_off, const int32_t **docno,
+                   const int32_t **freq, const double **score);
+int sme_query_near_device(sme_index *ix, const int32_t *term_ids, const int64_t *q_offsets, const int32_t *widths,
+                          const uint8_t *kinds, int nq, int order, int m, void *stream, const int64_t **d_res_off,
+                          const int32_t **d_docno, const int32_t **d_freq, const double **d_score, int64_t *total);
+int sme_query_near_stats(const sme_index *ix, uint64_t *candidates, uint64_t *verified, uint64_t *matches);
+
 /* Batched rank(): query q has term ids term_ids[q_offsets[q] .. q_offsets[q+1])
  * in query-token order (duplicates count twice, -1 entries are skipped; an id
  * outside [-1, V) is SME_EINVAL here and skipped like -1 by the device entry).

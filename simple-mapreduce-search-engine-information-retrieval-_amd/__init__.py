@@ -57,6 +57,7 @@ EXPORTS = [
     "sme_index_suggest_terms", "sme_index_suggest_terms_device", "sme_index_suggest_stats",
     "sme_query_boolean", "sme_query_boolean_device", "sme_query_boolean_stats",
     "sme_index_positions", "sme_query_phrase", "sme_query_phrase_device", "sme_query_phrase_stats",
+    "sme_query_near", "sme_query_near_device", "sme_query_near_stats",
 ]
 
 
@@ -153,6 +154,11 @@ def lib():
     L.sme_query_phrase_device.argtypes = [vp, i32p, i64p, C.c_int, C.c_int, C.c_int, vp, C.POINTER(vp), C.POINTER(vp),
                                           C.POINTER(vp), C.POINTER(vp), i64p]
     L.sme_query_phrase_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.sme_query_near.argtypes = [vp, i32p, i64p, i32p, u8p, C.c_int, C.c_int, C.c_int, C.POINTER(i64p), C.POINTER(i32p),
+                                 C.POINTER(i32p), C.POINTER(f64p)]
+    L.sme_query_near_device.argtypes = [vp, i32p, i64p, i32p, u8p, C.c_int, C.c_int, C.c_int, vp, C.POINTER(vp),
+                                        C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), i64p]
+    L.sme_query_near_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     _lib = L
     return L
 
@@ -727,6 +733,74 @@ class Index:
         _check(lib().sme_query_phrase_stats(self._h, C.byref(a), C.byref(b), C.byref(c)))
         return a.value, b.value, c.value
 
+    @staticmethod
+    def near_arrays(queries):
+        """The C-ABI's structure of a list of proximity queries, each (term_ids,
+        width, ordered): (term_ids int32, q_offsets int64[nq+1], widths int32[nq],
+        kinds uint8[nq]; kind 0 = ordered window, 1 = unordered)."""
+        terms, qoff, widths, kinds = [], [0], [], []
+        for ids, width, ordered in queries:
+            terms.extend(int(t) for t in ids)
+            qoff.append(len(terms))
+            widths.append(int(width))
+            kinds.append(0 if ordered else 1)
+        return (np.array(terms, np.int32), np.array(qoff, np.int64), np.array(widths, np.int32),
+                np.array(kinds, np.uint8))
+
+    @staticmethod
+    def _near_ptrs(term_ids, q_offsets, widths, kinds):
+        (t, o), ptrs = Index._phrase_ptrs(term_ids, q_offsets)
+        w = np.ascontiguousarray(widths, dtype=np.int32)
+        k = np.ascontiguousarray(kinds, dtype=np.uint8)
+        w = w if w.size else np.zeros(1, np.int32)
+        k = k if k.size else np.zeros(1, np.uint8)
+        return (t, o, w, k), ptrs + (w.ctypes.data_as(C.POINTER(C.c_int32)), k.ctypes.data_as(C.POINTER(C.c_uint8)))
+
+    def query_near(self, queries, order=0, m=0, arrays=None):
+        """sme_query_near: queries = a list of (term_ids, width, ordered), the ids
+        Index.lookup's (-1 = unknown, the query then has no result), at most 32.
+        ordered: every next term stands at most `width` positions after the
+        previous one (#od:width; width 1 is the exact phrase), freq = the distinct
+        end positions of such chains.  Not ordered: the set of the distinct terms
+        within `width` positions (#uw:width), freq = the positions of a query term
+        whose window of `width` positions ending there holds them all.  Within
+        one record, summed over the docno's records; score = (1 + ln freq) *
+        idf(matching documents).  Returns (res_off int64[nq+1], docno int32, freq
+        int32, score float64), ordered and cut as query_phrase's (include/sme.h).
+        The index must keep positions (Index.positions).
+        arrays: the structure as near_arrays returns it, instead of queries."""
+        a = arrays if arrays is not None else Index.near_arrays(queries)
+        n = len(a[1]) - 1
+        keep, ptrs = Index._near_ptrs(*a)
+        ro, dn, fq, sc = C.POINTER(C.c_int64)(), C.POINTER(C.c_int32)(), C.POINTER(C.c_int32)(), C.POINTER(C.c_double)()
+        _check(lib().sme_query_near(self._h, *ptrs, n, int(order), int(m), C.byref(ro), C.byref(dn), C.byref(fq),
+                                    C.byref(sc)))
+        off = np.ctypeslib.as_array(ro, (n + 1,)).copy()
+        total = int(off[n])
+        docno = np.ctypeslib.as_array(dn, (total,)).copy() if total else np.zeros(0, np.int32)
+        freq = np.ctypeslib.as_array(fq, (total,)).copy() if total else np.zeros(0, np.int32)
+        score = np.ctypeslib.as_array(sc, (total,)).copy() if total else np.zeros(0, np.float64)
+        return off, docno, freq, score
+
+    def query_near_device(self, queries, order=0, m=0, stream=None, arrays=None):
+        """sme_query_near_device: (device pointer of res_off int64[nq+1], of docno
+        int32[total], of freq int32[total], of score float64[total], total); the
+        arrays belong to the index until its next proximity call."""
+        a = arrays if arrays is not None else Index.near_arrays(queries)
+        keep, ptrs = Index._near_ptrs(*a)
+        ro, dn, fq, sc, tot = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int64()
+        _check(lib().sme_query_near_device(self._h, *ptrs, len(a[1]) - 1, int(order), int(m), C.c_void_p(stream or 0),
+                                           C.byref(ro), C.byref(dn), C.byref(fq), C.byref(sc), C.byref(tot)))
+        return ro.value or 0, dn.value or 0, fq.value or 0, sc.value or 0, tot.value
+
+    def near_stats(self):
+        """(candidates, verified, matches) of the last proximity call: the driver
+        postings examined, the (query, document) pairs whose records were
+        scanned, and the matches before the cut."""
+        a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        _check(lib().sme_query_near_stats(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
+
     def reweight(self, n_global, d_df_global=None, stream=None):
         """TF-IDF weights with all-reduced N (and df) of a doc-sharded index."""
         _check(lib().sme_index_reweight(self._h, n_global, C.c_void_p(d_df_global or 0), C.c_void_p(stream or 0)))
@@ -980,6 +1054,22 @@ class IntDocVectorsForwardIndex:
     def rank_phrase(self, k=10):
         """The first k documents (score desc, docno asc) holding get_phrase's phrase."""
         _, dn, _, _ = self.index.query_phrase([getattr(self, "_phrase", [])], order=1, m=k)
+        return [int(d) for d in dn]
+
+    def get_near(self, text, width, ordered=False):
+        """A proximity query from a text: processContent -> the term lookup, as
+        get_phrase (an unknown token stays as -1: no results), with the width and
+        whether the terms must stand in the text's order (#od:width) or only
+        within `width` positions of each other (#uw:width).  Sets the query for
+        rank_near() and returns it, (term_ids, width, ordered)."""
+        toks = self.index.ctx.process_content(text)
+        ids = [int(t) for t in self.index.lookup(toks)] if toks else []
+        self._near = (ids, int(width), bool(ordered))
+        return self._near
+
+    def rank_near(self, k=10):
+        """The first k documents (score desc, docno asc) matching get_near's query."""
+        _, dn, _, _ = self.index.query_near([getattr(self, "_near", ([], 1, False))], order=1, m=k)
         return [int(d) for d in dn]
 
     def rank(self, k=10):

@@ -983,6 +983,80 @@ int sme_query_phrase_stats(const sme_index *ix, uint64_t *candidates, uint64_t *
   });
 }
 
+// Proximity queries run over what phrase queries run over, and refuse what they refuse
+static void need_near_args(const sme_index *ix, const int32_t *term_ids, const int64_t *q_offsets,
+                           const int32_t *widths, const uint8_t *kinds, int nq, int order, int m) {
+  if (!ix || nq < 0 || (nq > 0 && (!q_offsets || !widths || !kinds))) throw sme::Error(SME_EINVAL, "bad argument");
+  if (ix->job != 0) throw sme::Error(SME_EINVAL, "proximity query: not a TermKGramDocIndexer index");
+  if (ix->records_only)
+    throw sme::Error(SME_EINVAL, "proximity query: the index has no query side (merged shard pieces)");
+  if (ix->K != 1) throw sme::Error(SME_EINVAL, "proximity query: the index holds k-grams (K != 1), not terms");
+  if (!ix->has_positions)
+    throw sme::Error(SME_EINVAL,
+                     "proximity query: the index keeps no positions (build it with option \"positions\" 1)");
+  if (m < 0) throw sme::Error(SME_EINVAL, "proximity query: m must be >= 0");
+  if (order != 0 && order != 1) throw sme::Error(SME_EINVAL, "proximity query: order must be 0 (docno) or 1 (score)");
+  // term_ids may be NULL only in a batch without a term (sme::query_near validates
+  // the offsets themselves before anything is read through them)
+  if (nq > 0 && q_offsets[nq] != 0 && !term_ids) throw sme::Error(SME_EINVAL, "bad argument");
+}
+
+int sme_query_near_device(sme_index *ix, const int32_t *term_ids, const int64_t *q_offsets, const int32_t *widths,
+                          const uint8_t *kinds, int nq, int order, int m, void *stream, const int64_t **d_res_off,
+                          const int32_t **d_docno, const int32_t **d_freq, const double **d_score, int64_t *total) {
+  return guard([&] {
+    if (!d_res_off || !d_docno || !d_freq || !d_score) throw sme::Error(SME_EINVAL, "null argument");
+    need_near_args(ix, term_ids, q_offsets, widths, kinds, nq, order, m);
+    set_device(ix->ctx);
+    sme::query_near(ix, term_ids, q_offsets, widths, kinds, nq, order, m, stream_of(ix->ctx, stream));
+    *d_res_off = (const int64_t *)ix->d_nq_off.p;
+    *d_docno = (const int32_t *)ix->d_nq_docno.p;
+    *d_freq = (const int32_t *)ix->d_nq_freq.p;
+    *d_score = (const double *)ix->d_nq_score.p;
+    if (total) *total = ix->nq_total;
+  });
+}
+
+int sme_query_near(sme_index *ix, const int32_t *term_ids, const int64_t *q_offsets, const int32_t *widths,
+                   const uint8_t *kinds, int nq, int order, int m, const int64_t **res_off, const int32_t **docno,
+                   const int32_t **freq, const double **score) {
+  return guard([&] {
+    if (!res_off || !docno || !freq || !score) throw sme::Error(SME_EINVAL, "null argument");
+    need_near_args(ix, term_ids, q_offsets, widths, kinds, nq, order, m);
+    set_device(ix->ctx);
+    hipStream_t st = ix->ctx->own_stream;
+    sme::query_near(ix, term_ids, q_offsets, widths, kinds, nq, order, m, st);
+    const size_t tot = (size_t)ix->nq_total;
+    ix->h_nq_off.resize((size_t)nq + 1);
+    ix->h_nq_docno.resize(tot + 1);  // (never an empty vector: data() stays a valid pointer)
+    ix->h_nq_freq.resize(tot + 1);
+    ix->h_nq_score.resize(tot + 1);
+    SME_HIP(hipMemcpyAsync(ix->h_nq_off.data(), ix->d_nq_off.p, ((size_t)nq + 1) * sizeof(int64_t),
+                           hipMemcpyDeviceToHost, st));
+    if (tot) {
+      SME_HIP(hipMemcpyAsync(ix->h_nq_docno.data(), ix->d_nq_docno.p, tot * sizeof(int32_t), hipMemcpyDeviceToHost,
+                             st));
+      SME_HIP(hipMemcpyAsync(ix->h_nq_freq.data(), ix->d_nq_freq.p, tot * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+      SME_HIP(hipMemcpyAsync(ix->h_nq_score.data(), ix->d_nq_score.p, tot * sizeof(double), hipMemcpyDeviceToHost,
+                             st));
+    }
+    SME_HIP(hipStreamSynchronize(st));
+    *res_off = ix->h_nq_off.data();
+    *docno = ix->h_nq_docno.data();
+    *freq = ix->h_nq_freq.data();
+    *score = ix->h_nq_score.data();
+  });
+}
+
+int sme_query_near_stats(const sme_index *ix, uint64_t *candidates, uint64_t *verified, uint64_t *matches) {
+  return guard([&] {
+    if (!ix || !candidates || !verified || !matches) throw sme::Error(SME_EINVAL, "null argument");
+    *candidates = ix->nq_cands;
+    *verified = ix->nq_verified;
+    *matches = ix->nq_matches;
+  });
+}
+
 int sme_index_positions(const sme_index *ix, uint64_t *records, uint64_t *positions, uint64_t *bytes) {
   return guard([&] {
     if (!ix || !records || !positions || !bytes) throw sme::Error(SME_EINVAL, "null argument");

@@ -208,6 +208,21 @@ struct sme_index {
   std::vector<int64_t> h_pq_off;
   std::vector<int32_t> h_pq_docno, h_pq_freq;
   std::vector<double> h_pq_score;
+  // proximity queries (sme_near.hip): the last call's outputs and counts, as for
+  // phrases, and the scorer table 1 + ln(f) for f < nq_lut_n -- d_lut's bits
+  // continued past max_tf (an unordered freq can pass it); filled on first use, it only grows
+  sme::DevBuf d_nq_off;    // int64 [nq + 1]  result offsets
+  sme::DevBuf d_nq_docno;  // int32 [total]   matching documents
+  sme::DevBuf d_nq_freq;   // int32 [total]   the query's count in each
+  sme::DevBuf d_nq_score;  // double [total]  their scores
+  sme::DevBuf d_nq_lut;    // double [nq_lut_n]
+  int64_t nq_lut_n = 0;
+  int64_t nq_max_span = -1;  // the most stream positions of one docno (-1: not yet found), a bound on any freq
+  int64_t nq_total = 0;
+  uint64_t nq_cands = 0, nq_verified = 0, nq_matches = 0;  // driver postings; filter survivors; matches before the cut
+  std::vector<int64_t> h_nq_off;
+  std::vector<int32_t> h_nq_docno, h_nq_freq;
+  std::vector<double> h_nq_score;
   // stage timings of the build that produced this index (ms)
   std::vector<std::pair<std::string, float>> profile;
   ~sme_index() { ctx->live_indexes--; }  // members (pooled buffers) are released after this body
@@ -217,7 +232,8 @@ struct sme_index {
                            &d_tf_o, &d_rec_docno, &d_rec_first, &d_ser, &d_hrow_of, &d_heavy, &d_spk, &d_wkeys, &d_wgoff,
                            &d_wgterm, &d_wx_off, &d_wx_ids, &d_wx_in, &d_wx_plan, &d_wx_choff, &d_wx_moff, &d_wx_scan, &d_fz_off,
                            &d_fz_ids, &d_fz_dist, &d_bq_off, &d_bq_docno, &d_bq_score, &d_ps_off, &d_ps_terms, &d_ps_docno,
-                           &d_pq_off, &d_pq_docno, &d_pq_freq, &d_pq_score})
+                           &d_pq_off, &d_pq_docno, &d_pq_freq, &d_pq_score, &d_nq_off, &d_nq_docno, &d_nq_freq, &d_nq_score,
+                           &d_nq_lut})
       b->pool = &c->pool;
   }
 };
@@ -396,6 +412,12 @@ void query_boolean(sme_index *ix, const int32_t *term_ids, const int64_t *g_offs
 // pq_total, and the call's counts pq_cands / pq_verified / pq_matches
 void query_phrase(sme_index *ix, const int32_t *term_ids, const int64_t *p_offsets, int np, int order, int m,
                   hipStream_t st);
+// proximity queries (sme_near.hip): nq queries of term ids with a width and a kind
+// each (0 ordered window, 1 unordered; host arrays, validated here) over the same
+// positions, through the same pass -> ix->d_nq_off / d_nq_docno / d_nq_freq /
+// d_nq_score / nq_total, and the call's counts nq_cands / nq_verified / nq_matches
+void query_near(sme_index *ix, const int32_t *term_ids, const int64_t *q_offsets, const int32_t *widths,
+                const uint8_t *kinds, int nq, int order, int m, hipStream_t st);
 // The idf of a term with document frequency df among N documents, the one
 // expression behind the build's idf tables (idf_by_df[df] = idf_value(N, df),
 // idf_by_q[q] = idf_value(q, 1) read at q = N / df: log10 of the integer quotient)
