@@ -150,6 +150,9 @@ void sme_destroy(sme_ctx *ctx);
  *                   record's term stream with the index (sme_index_positions), which phrase
  *                   queries (sme_query_phrase) need.  Every other output of the build is the
  *                   same bytes; "bool_chunk" also cuts a phrase query's candidates
+ *   "struct_narrow" structured queries (sme_query_structured): 1 (default) a query's required
+ *                   term-only groups cut its operator leaves' candidates before their records
+ *                   are scanned, 0 every leaf is evaluated whole.  Results are the same
  * Unknown names and out-of-range values are SME_EINVAL. */
 int sme_set_option(sme_ctx *ctx, const char *name, int64_t value);
 
@@ -549,6 +552,88 @@ int sme_query_near_device(sme_index *ix, const int32_t *term_ids, const int64_t 
                           const uint8_t *kinds, int nq, int order, int m, void *stream, const int64_t **d_res_off,
                           const int32_t **d_docno, const int32_t **d_freq, const double **d_score, int64_t *total);
 int sme_query_near_stats(const sme_index *ix, uint64_t *candidates, uint64_t *verified, uint64_t *matches);
+
+/* Structured queries: Boolean retrieval whose group members are LEAVES -- a term,
+ * or a phrase / window over terms -- so that one call answers and scores a query
+ * such as `"new york" hotel* -"times square"` or `#uw:8(network protocol) tcp|udp`.
+ * It is sme_query_boolean's three-level structure with one more level below the
+ * slot.  Query i's groups are [q_offsets[i], q_offsets[i + 1]); group g's leaves
+ * are [g_offsets[g], g_offsets[g + 1]) and its flag is g_flags[g] (0 required, 1
+ * excluded); leaf l's term ids are term_ids[l_offsets[l] .. l_offsets[l + 1]), its
+ * kind l_kinds[l] and its width l_widths[l].  All host arrays, every offset array
+ * ascending from 0.
+ *
+ * Kind 0, a term: exactly one id.  The leaf's document list is the term's posting
+ * list, its value at a document d_weight at that posting; its width is not read;
+ * id -1 is an empty list, as in sme_query_boolean.
+ * Kind 1, the ordered window #od:N, and kind 2, the unordered window #uw:N, with
+ * N = l_widths[l], over 1 to 32 ids: the list is the documents sme_query_near
+ * returns for that query (its kind 0 / 1) with its freq, the value the score
+ * sme_query_near gives, bit for bit: (1 + ln freq) * idf(df), df the leaf's matching
+ * documents over the whole index, idf as the weights form it in the index's idf
+ * mode, N_docs as of the last sme_index_reweight.  A phrase is kind 1 with width
+ * 1.  An operator leaf without ids, or holding -1, is an empty list.
+ *
+ * A document matches a query exactly by sme_query_boolean's rules with "posting
+ * list" read as "leaf's document list": it lies in at least one list of every
+ * required group and in no list of an excluded one; a query without a required
+ * group and the empty query match nothing.  Its score is the fp64 sum from 0.0 of
+ * the leaves' values at the document over every leaf of every required group in
+ * listed order; a leaf listed twice counts twice, a leaf that does not hold the
+ * document adds nothing, excluded leaves add nothing.  order 0 / 1 and the cut m
+ * are sme_query_boolean's.  So a batch of term leaves only is sme_query_boolean,
+ * one required group holding one operator leaf is sme_query_near, and an ordered
+ * leaf of one term (any width) has the value of the term leaf.
+ * Query i's results are docno[] / score[] at [res_off[i], res_off[i + 1]); nq + 1
+ * offsets, owned by the index until the next structured call on it (host memory
+ * from the host entry; device memory from the device entry, with *total =
+ * res_off[nq], total may be NULL).  A structured call leaves the buffers of the
+ * last wildcard, suggestion, Boolean, phrase and proximity call alone, and the
+ * other way round.  nq == 0 is valid.
+ *
+ * A batch of term leaves only needs a query side and nothing else, as
+ * sme_query_boolean (loaded indexes, K >= 2).  With any operator leaf in the batch
+ * the index must keep positions and have K = 1: otherwise SME_EINVAL with
+ * sme_query_near's message for the case.
+ * Limits (SME_ELIMIT, the message names the query): more than 64 groups or more
+ * than 1024 leaves in a query, more than 32 ids in an operator leaf; also 2^31 or
+ * more ids or leaves in a batch, sme_query_near's 2^31 candidate documents over the
+ * batch's operator leaves, and 2^31 or more matches in a batch before the cut.
+ * SME_EINVAL (the message names the query): a term leaf with other than one id, a
+ * kind outside 0 .. 2, an operator width below 1, an id outside [-1, V), a flag
+ * other than 0 / 1, offsets at any level that do not ascend from 0 or do not agree
+ * with the level above; also m < 0 and an order other than 0 / 1.  q_offsets,
+ * g_offsets and l_offsets are never NULL when nq > 0; the other arrays may be NULL
+ * only in a batch without a group -- a NULL array otherwise is SME_EINVAL.  Every
+ * level's offsets are checked before anything is read through them.
+ *
+ * Evaluation: the batch's operator leaves go through sme_query_near's pass once
+ * (docno order, uncut); the Boolean stage then reads them beside the posting
+ * lists, its driver the required group with the fewest entries ("bool_driver",
+ * "bool_chunk" as for sme_query_boolean).  Narrowing (option "struct_narrow", on
+ * by default): a document outside any required group that holds term leaves only
+ * cannot be a result, so an operator leaf of that query -- required or excluded,
+ * alone or in an OR group -- is not verified there: its candidates are also tested
+ * against those groups (the first 16 of them in listed order, skipping a group
+ * that would take the slots past 256) before their records are scanned.  Only in
+ * SME_IDF_REFERENCE: in the true-df mode a leaf's score needs its full df, leaves
+ * are evaluated whole and the option is ignored.  The results never depend on the
+ * option; only *verified does.
+ * sme_query_structured_stats reports on the last structured call on the index:
+ * *leaves = the operator leaves evaluated, *verified = the (leaf, document) pairs
+ * whose records were scanned, *candidates = the Boolean stage's driver entries
+ * examined, *matches = the matches before the cut. */
+int sme_query_structured(sme_index *ix, const int32_t *term_ids, const int64_t *l_offsets, const uint8_t *l_kinds,
+                         const int32_t *l_widths, const int64_t *g_offsets, const uint8_t *g_flags,
+                         const int64_t *q_offsets, int nq, int order, int m, const int64_t **res_off,
+                         const int32_t **docno, const double **score);
+int sme_query_structured_device(sme_index *ix, const int32_t *term_ids, const int64_t *l_offsets,
+                                const uint8_t *l_kinds, const int32_t *l_widths, const int64_t *g_offsets,
+                                const uint8_t *g_flags, const int64_t *q_offsets, int nq, int order, int m,
+                                void *stream, const int64_t **d_res_off, const int32_t **d_docno,
+                                const double **d_score, int64_t *total);
+int sme_query_structured_stats(const sme_index *ix, uint64_t *leaves, uint64_t *verified, uint64_t *candidates,
+                               uint64_t *matches);
 
 /* Batched rank(): query q has term ids term_ids[q_offsets[q] .. q_offsets[q+1])
  * in query-token order (duplicates count twice, -1 entries are skipped; an id

@@ -58,6 +58,7 @@ EXPORTS = [
     "sme_query_boolean", "sme_query_boolean_device", "sme_query_boolean_stats",
     "sme_index_positions", "sme_query_phrase", "sme_query_phrase_device", "sme_query_phrase_stats",
     "sme_query_near", "sme_query_near_device", "sme_query_near_stats",
+    "sme_query_structured", "sme_query_structured_device", "sme_query_structured_stats",
 ]
 
 
@@ -159,6 +160,12 @@ def lib():
     L.sme_query_near_device.argtypes = [vp, i32p, i64p, i32p, u8p, C.c_int, C.c_int, C.c_int, vp, C.POINTER(vp),
                                         C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), i64p]
     L.sme_query_near_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.sme_query_structured.argtypes = [vp, i32p, i64p, u8p, i32p, i64p, u8p, i64p, C.c_int, C.c_int, C.c_int,
+                                       C.POINTER(i64p), C.POINTER(i32p), C.POINTER(f64p)]
+    L.sme_query_structured_device.argtypes = [vp, i32p, i64p, u8p, i32p, i64p, u8p, i64p, C.c_int, C.c_int, C.c_int,
+                                              vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), i64p]
+    L.sme_query_structured_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                             C.POINTER(C.c_uint64)]
     _lib = L
     return L
 
@@ -801,6 +808,87 @@ class Index:
         _check(lib().sme_query_near_stats(self._h, C.byref(a), C.byref(b), C.byref(c)))
         return a.value, b.value, c.value
 
+    @staticmethod
+    def structured_arrays(queries):
+        """The C-ABI's four-level structure of a list of queries, each a list of
+        (leaves, excluded) groups, a leaf being (term_ids, kind, width) -- kind 0 a
+        term (one id; the width is not read), 1 the ordered window #od:width, 2 the
+        unordered window #uw:width: (term_ids int32, l_offsets int64[nleaves+1],
+        l_kinds uint8[nleaves], l_widths int32[nleaves], g_offsets
+        int64[ngroups+1], g_flags uint8[ngroups], q_offsets int64[nq+1])."""
+        terms, loff, kinds, widths, goff, flags, qoff = [], [0], [], [], [0], [], [0]
+        for groups in queries:
+            for leaves, excluded in groups:
+                for ids, kind, width in leaves:
+                    terms.extend(int(t) for t in ids)
+                    loff.append(len(terms))
+                    kinds.append(int(kind))
+                    widths.append(int(width))
+                goff.append(len(kinds))
+                flags.append(int(excluded))
+            qoff.append(len(flags))
+        return (np.array(terms, np.int32), np.array(loff, np.int64), np.array(kinds, np.uint8),
+                np.array(widths, np.int32), np.array(goff, np.int64), np.array(flags, np.uint8),
+                np.array(qoff, np.int64))
+
+    @staticmethod
+    def _structured_ptrs(arrays):
+        # (an empty numpy array may hand out any pointer: keep one element behind each)
+        keep, ptrs = [], []
+        for a, dt, ct in zip(arrays, (np.int32, np.int64, np.uint8, np.int32, np.int64, np.uint8, np.int64),
+                             (C.c_int32, C.c_int64, C.c_uint8, C.c_int32, C.c_int64, C.c_uint8, C.c_int64)):
+            a = np.ascontiguousarray(a, dtype=dt)
+            a = a if a.size else np.zeros(1, dt)
+            keep.append(a)
+            ptrs.append(a.ctypes.data_as(C.POINTER(ct)))
+        return keep, ptrs
+
+    def query_structured(self, queries, order=0, m=0, arrays=None):
+        """sme_query_structured: queries = a list of queries, each a list of
+        (leaves, excluded) groups; a leaf is (term_ids, kind, width): kind 0 a term
+        (one id, -1 = an empty list), kind 1 the ordered window #od:width (width 1:
+        the phrase), kind 2 the unordered window #uw:width, over at most 32 ids.
+        A leaf's document list is the term's postings, or what query_near returns
+        for the window; a document matches by query_boolean's rules over those
+        lists, and its score is the fp64 sum, in listed order, of the required
+        leaves' values -- the term's weight, the window's query_near score.
+        Returns (res_off int64[nq+1], docno int32, score float64), ordered and
+        cut as query_boolean's (include/sme.h).  A batch with a window needs an
+        index that keeps positions (Index.positions).
+        arrays: the structure as structured_arrays returns it, instead of queries."""
+        a = arrays if arrays is not None else Index.structured_arrays(queries)
+        nq = len(a[6]) - 1
+        keep, ptrs = Index._structured_ptrs(a)
+        ro, dn, sc = C.POINTER(C.c_int64)(), C.POINTER(C.c_int32)(), C.POINTER(C.c_double)()
+        _check(lib().sme_query_structured(self._h, *ptrs, nq, int(order), int(m), C.byref(ro), C.byref(dn),
+                                          C.byref(sc)))
+        off = np.ctypeslib.as_array(ro, (nq + 1,)).copy()
+        total = int(off[nq])
+        docno = np.ctypeslib.as_array(dn, (total,)).copy() if total else np.zeros(0, np.int32)
+        score = np.ctypeslib.as_array(sc, (total,)).copy() if total else np.zeros(0, np.float64)
+        return off, docno, score
+
+    def query_structured_device(self, queries, order=0, m=0, stream=None, arrays=None):
+        """sme_query_structured_device: (device pointer of res_off int64[nq+1], of
+        docno int32[total], of score float64[total], total); the arrays belong to
+        the index until its next structured call."""
+        a = arrays if arrays is not None else Index.structured_arrays(queries)
+        keep, ptrs = Index._structured_ptrs(a)
+        ro, dn, sc, tot = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int64()
+        _check(lib().sme_query_structured_device(self._h, *ptrs, len(a[6]) - 1, int(order), int(m),
+                                                 C.c_void_p(stream or 0), C.byref(ro), C.byref(dn), C.byref(sc),
+                                                 C.byref(tot)))
+        return ro.value or 0, dn.value or 0, sc.value or 0, tot.value
+
+    def structured_stats(self):
+        """(leaves, verified, candidates, matches) of the last structured call: the
+        operator leaves evaluated, the (leaf, document) pairs whose records were
+        scanned, the Boolean stage's driver entries examined, and the matches
+        before the cut."""
+        a, b, c, d = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+        _check(lib().sme_query_structured_stats(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
+        return a.value, b.value, c.value, d.value
+
     def reweight(self, n_global, d_df_global=None, stream=None):
         """TF-IDF weights with all-reduced N (and df) of a doc-sharded index."""
         _check(lib().sme_index_reweight(self._h, n_global, C.c_void_p(d_df_global or 0), C.c_void_p(stream or 0)))
@@ -932,6 +1020,75 @@ class CharKGramTermIndexer:
                 with open(os.path.join(output_dir, "part-%05d" % p), "wb") as f:
                     f.write(out.partition_text(p))
         return out
+
+
+def _split_outside(text, seps, what):
+    """text cut at the characters of seps (None: whitespace) that stand outside
+    "..." and (...); unbalanced quotes or parentheses are a ValueError."""
+    parts, cur, quoted, depth = [], [], False, 0
+    for ch in text:
+        if ch == '"':
+            quoted = not quoted
+        elif not quoted and ch == "(":
+            depth += 1
+        elif not quoted and ch == ")":
+            depth -= 1
+            if depth < 0:
+                raise ValueError("structured query: ')' without '(' in %r" % what)
+        if not quoted and depth == 0 and (ch.isspace() if seps is None else ch in seps):
+            parts.append("".join(cur))
+            cur = []
+        else:
+            cur.append(ch)
+    if quoted:
+        raise ValueError("structured query: unbalanced '\"' in %r" % what)
+    if depth:
+        raise ValueError("structured query: unbalanced '(' in %r" % what)
+    parts.append("".join(cur))
+    return parts
+
+
+def parse_structured(text):
+    """The structure of a query text, no index needed: a list of groups (leaves,
+    excluded), every leaf a (kind, text, width) of strings -- ("term", word, 0),
+    ("od", words, N) or ("uw", words, N).
+
+    The text is split on whitespace outside quotes and parentheses; every piece is
+    one group:
+      -piece          a leading '-' excludes the group
+      a|b|"c d"       '|' without spaces joins alternatives into one OR group
+      "new york"      a phrase: the ordered window of width 1, ("od", "new york", 1)
+      #od:N(a b c)    the ordered window: each next term at most N positions on
+      #uw:N(a b c)    the unordered window: all the terms within N positions
+      word            anything else, wildcards ('*', '?') included: ("term", word, 0)
+    Unbalanced quotes or parentheses, an empty alternative, a window without a
+    width of at least 1 and quotes or parentheses inside a word are a ValueError.
+    IntDocVectorsForwardIndex.get_structured turns the strings into term ids."""
+    import re
+    groups = []
+    for piece in _split_outside(text, None, text):
+        if not piece:
+            continue
+        excluded = piece.startswith("-")
+        leaves = []
+        for alt in _split_outside(piece[1:] if excluded else piece, "|", piece):
+            if not alt:
+                raise ValueError("structured query: an empty alternative in %r" % piece)
+            win = re.match(r"^#(od|uw):(\d+)\((.*)\)$", alt, re.S)
+            if alt.startswith('"'):
+                if len(alt) < 2 or not alt.endswith('"') or '"' in alt[1:-1]:
+                    raise ValueError("structured query: text beside a quoted phrase in %r" % piece)
+                leaves.append(("od", alt[1:-1], 1))
+            elif win:
+                if int(win.group(2)) < 1 or "(" in win.group(3) or ")" in win.group(3) or '"' in win.group(3):
+                    raise ValueError("structured query: a malformed window in %r" % piece)
+                leaves.append((win.group(1), win.group(3), int(win.group(2))))
+            elif alt.startswith("#") or any(c in alt for c in '"()'):
+                raise ValueError("structured query: a malformed leaf in %r" % piece)
+            else:
+                leaves.append(("term", alt, 0))
+        groups.append((leaves, excluded))
+    return groups
 
 
 class IntDocVectorsForwardIndex:
@@ -1070,6 +1227,50 @@ class IntDocVectorsForwardIndex:
     def rank_near(self, k=10):
         """The first k documents (score desc, docno asc) matching get_near's query."""
         _, dn, _, _ = self.index.query_near([getattr(self, "_near", ([], 1, False))], order=1, m=k)
+        return [int(d) for d in dn]
+
+    def get_structured(self, text):
+        """A structured query from a text in parse_structured's syntax:
+        `"new york" hotel* -"times square"`, `#uw:8(network protocol) tcp|udp`.
+        A word holding '*' or '?' is lower-cased and expanded
+        (Index.expand_wildcards) into term leaves of its group; any other word
+        goes through processContent -- standing alone, every token it yields is a
+        group of its own (a word that yields none, a stop word, is dropped; an
+        unknown token is -1), in an OR group its tokens join the group, all as
+        get_boolean does.  Phrase and window texts go through processContent and
+        the lookup as get_phrase's (an unknown token stays -1: the leaf is empty).
+        Sets the query for rank_structured() and returns it, a list of (leaves,
+        excluded) with leaves (term_ids, kind, width) as Index.query_structured
+        takes them.  A window needs an index that keeps positions."""
+        kinds = {"od": 1, "uw": 2}
+        groups = []
+        for leaves, excluded in parse_structured(text):
+            out, had_other = [], False
+            for kind, body, width in leaves:
+                if kind != "term":
+                    toks = self.index.ctx.process_content(body)
+                    ids = [int(t) for t in self.index.lookup(toks)] if toks else []
+                    out.append((ids, kinds[kind], width))
+                    had_other = True
+                elif "*" in body or "?" in body:
+                    _, ids = self.index.expand_wildcards([body.lower()])
+                    out.extend(([int(t)], 0, 0) for t in ids)
+                    had_other = True
+                else:
+                    toks = self.index.ctx.process_content(body)
+                    ids = [int(t) for t in self.index.lookup(toks)] if toks else []
+                    if len(leaves) == 1:  # a word alone: a group per token
+                        groups.extend(([([t], 0, 0)], excluded) for t in ids)
+                    else:
+                        out.extend(([t], 0, 0) for t in ids)
+            if out or had_other:
+                groups.append((out, excluded))
+        self._structured = groups
+        return groups
+
+    def rank_structured(self, k=10):
+        """The first k documents (score desc, docno asc) matching get_structured's query."""
+        _, dn, _ = self.index.query_structured([getattr(self, "_structured", [])], order=1, m=k)
         return [int(d) for d in dn]
 
     def rank(self, k=10):

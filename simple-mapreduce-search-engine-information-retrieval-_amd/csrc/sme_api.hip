@@ -356,6 +356,9 @@ int sme_set_option(sme_ctx *cx, const char *name, int64_t v) {
     } else if (n == "positions") {
       range(0, 1);
       cx->opt_positions = v;
+    } else if (n == "struct_narrow") {
+      range(0, 1);
+      cx->opt_struct_narrow = v;
     } else {
       throw sme::Error(SME_EINVAL, "unknown option " + n);
     }
@@ -1054,6 +1057,84 @@ int sme_query_near_stats(const sme_index *ix, uint64_t *candidates, uint64_t *ve
     *candidates = ix->nq_cands;
     *verified = ix->nq_verified;
     *matches = ix->nq_matches;
+  });
+}
+
+// Structured queries run over what Boolean retrieval runs over; a batch with an
+// operator leaf also needs what proximity queries need (sme::query_structured
+// says so once it has validated the batch and knows its leaves)
+static void need_structured_args(const sme_index *ix, const int32_t *term_ids, const int64_t *l_offsets,
+                                 const uint8_t *l_kinds, const int32_t *l_widths, const int64_t *g_offsets,
+                                 const uint8_t *g_flags, const int64_t *q_offsets, int nq, int order, int m) {
+  if (!ix || nq < 0 || (nq > 0 && !q_offsets)) throw sme::Error(SME_EINVAL, "bad argument");
+  if (ix->job != 0) throw sme::Error(SME_EINVAL, "structured query: not a TermKGramDocIndexer index");
+  need_query_side(ix);
+  if (m < 0) throw sme::Error(SME_EINVAL, "structured query: m must be >= 0");
+  if (order != 0 && order != 1)
+    throw sme::Error(SME_EINVAL, "structured query: order must be 0 (docno) or 1 (score)");
+  // g_offsets and l_offsets always hold an entry; only a batch without a group may
+  // leave the other arrays NULL (sme::query_structured validates the offsets
+  // themselves before anything is read through them)
+  if (nq > 0 && (!g_offsets || !l_offsets ||
+                 (q_offsets[nq] != 0 && (!g_flags || !term_ids || !l_kinds || !l_widths))))
+    throw sme::Error(SME_EINVAL, "bad argument");
+}
+
+int sme_query_structured_device(sme_index *ix, const int32_t *term_ids, const int64_t *l_offsets,
+                                const uint8_t *l_kinds, const int32_t *l_widths, const int64_t *g_offsets,
+                                const uint8_t *g_flags, const int64_t *q_offsets, int nq, int order, int m,
+                                void *stream, const int64_t **d_res_off, const int32_t **d_docno,
+                                const double **d_score, int64_t *total) {
+  return guard([&] {
+    if (!d_res_off || !d_docno || !d_score) throw sme::Error(SME_EINVAL, "null argument");
+    need_structured_args(ix, term_ids, l_offsets, l_kinds, l_widths, g_offsets, g_flags, q_offsets, nq, order, m);
+    set_device(ix->ctx);
+    sme::query_structured(ix, term_ids, l_offsets, l_kinds, l_widths, g_offsets, g_flags, q_offsets, nq, order, m,
+                          stream_of(ix->ctx, stream));
+    *d_res_off = (const int64_t *)ix->d_sq_off.p;
+    *d_docno = (const int32_t *)ix->d_sq_docno.p;
+    *d_score = (const double *)ix->d_sq_score.p;
+    if (total) *total = ix->sq_total;
+  });
+}
+
+int sme_query_structured(sme_index *ix, const int32_t *term_ids, const int64_t *l_offsets, const uint8_t *l_kinds,
+                         const int32_t *l_widths, const int64_t *g_offsets, const uint8_t *g_flags,
+                         const int64_t *q_offsets, int nq, int order, int m, const int64_t **res_off,
+                         const int32_t **docno, const double **score) {
+  return guard([&] {
+    if (!res_off || !docno || !score) throw sme::Error(SME_EINVAL, "null argument");
+    need_structured_args(ix, term_ids, l_offsets, l_kinds, l_widths, g_offsets, g_flags, q_offsets, nq, order, m);
+    set_device(ix->ctx);
+    hipStream_t st = ix->ctx->own_stream;
+    sme::query_structured(ix, term_ids, l_offsets, l_kinds, l_widths, g_offsets, g_flags, q_offsets, nq, order, m, st);
+    const size_t tot = (size_t)ix->sq_total;
+    ix->h_sq_off.resize((size_t)nq + 1);
+    ix->h_sq_docno.resize(tot + 1);  // (never an empty vector: data() stays a valid pointer)
+    ix->h_sq_score.resize(tot + 1);
+    SME_HIP(hipMemcpyAsync(ix->h_sq_off.data(), ix->d_sq_off.p, ((size_t)nq + 1) * sizeof(int64_t),
+                           hipMemcpyDeviceToHost, st));
+    if (tot) {
+      SME_HIP(hipMemcpyAsync(ix->h_sq_docno.data(), ix->d_sq_docno.p, tot * sizeof(int32_t), hipMemcpyDeviceToHost,
+                             st));
+      SME_HIP(hipMemcpyAsync(ix->h_sq_score.data(), ix->d_sq_score.p, tot * sizeof(double), hipMemcpyDeviceToHost,
+                             st));
+    }
+    SME_HIP(hipStreamSynchronize(st));
+    *res_off = ix->h_sq_off.data();
+    *docno = ix->h_sq_docno.data();
+    *score = ix->h_sq_score.data();
+  });
+}
+
+int sme_query_structured_stats(const sme_index *ix, uint64_t *leaves, uint64_t *verified, uint64_t *candidates,
+                               uint64_t *matches) {
+  return guard([&] {
+    if (!ix || !leaves || !verified || !candidates || !matches) throw sme::Error(SME_EINVAL, "null argument");
+    *leaves = ix->sq_leaves;
+    *verified = ix->sq_verified;
+    *candidates = ix->sq_cands;
+    *matches = ix->sq_matches;
   });
 }
 

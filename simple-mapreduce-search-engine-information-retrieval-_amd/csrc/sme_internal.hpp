@@ -73,6 +73,7 @@ struct sme_ctx {
   int64_t opt_bool_chunk = 1024;  // "bool_chunk": Boolean-query candidates per workgroup (64..4096, multiples of 64)
   int64_t opt_bool_driver = 0;    // "bool_driver": 0 = the required group with the fewest postings drives, 1 = the first
   int64_t opt_positions = 0;      // "positions": 1 = a K = 1 build keeps every record's term stream (phrase queries)
+  int64_t opt_struct_narrow = 1;  // "struct_narrow": 1 = a structured query's term groups cut its operator leaves' candidates
   int64_t opt_corpus_keep = int64_t(16) << 30;  // "corpus_keep_bytes": host-corpus builds keep their device copy
                                                 // (no hipMalloc next build) only up to this size
   // pinned host staging of device -> host record copies into pageable caller
@@ -223,6 +224,24 @@ struct sme_index {
   std::vector<int64_t> h_nq_off;
   std::vector<int32_t> h_nq_docno, h_nq_freq;
   std::vector<double> h_nq_score;
+  // structured queries (sme_structq.hip): the last call's outputs and counts, and
+  // the virtual posting lists of its operator leaves -- leaf i's documents (docno
+  // ascending) and values at [d_sv_off[i], d_sv_off[i + 1]), written by the
+  // proximity pass (sv_*: that pass's counts)
+  sme::DevBuf d_sq_off;    // int64 [nq + 1]  result offsets
+  sme::DevBuf d_sq_docno;  // int32 [total]   matching documents
+  sme::DevBuf d_sq_score;  // double [total]  their scores
+  sme::DevBuf d_sv_off;    // int64 [leaves + 1]
+  sme::DevBuf d_sv_docno;  // int32 [sv_total]
+  sme::DevBuf d_sv_freq;   // int32 [sv_total]
+  sme::DevBuf d_sv_score;  // double [sv_total]
+  int64_t sq_total = 0, sv_total = 0;
+  uint64_t sv_cands = 0, sv_verified = 0, sv_matches = 0;
+  // operator leaves evaluated; (leaf, document) pairs scanned; driver entries examined; matches before the cut
+  uint64_t sq_leaves = 0, sq_verified = 0, sq_cands = 0, sq_matches = 0;
+  std::vector<int64_t> h_sq_off;
+  std::vector<int32_t> h_sq_docno;
+  std::vector<double> h_sq_score;
   // stage timings of the build that produced this index (ms)
   std::vector<std::pair<std::string, float>> profile;
   ~sme_index() { ctx->live_indexes--; }  // members (pooled buffers) are released after this body
@@ -233,7 +252,7 @@ struct sme_index {
                            &d_wgterm, &d_wx_off, &d_wx_ids, &d_wx_in, &d_wx_plan, &d_wx_choff, &d_wx_moff, &d_wx_scan, &d_fz_off,
                            &d_fz_ids, &d_fz_dist, &d_bq_off, &d_bq_docno, &d_bq_score, &d_ps_off, &d_ps_terms, &d_ps_docno,
                            &d_pq_off, &d_pq_docno, &d_pq_freq, &d_pq_score, &d_nq_off, &d_nq_docno, &d_nq_freq, &d_nq_score,
-                           &d_nq_lut})
+                           &d_nq_lut, &d_sq_off, &d_sq_docno, &d_sq_score, &d_sv_off, &d_sv_docno, &d_sv_freq, &d_sv_score})
       b->pool = &c->pool;
   }
 };
@@ -418,6 +437,39 @@ void query_phrase(sme_index *ix, const int32_t *term_ids, const int64_t *p_offse
 // d_nq_score / nq_total, and the call's counts nq_cands / nq_verified / nq_matches
 void query_near(sme_index *ix, const int32_t *term_ids, const int64_t *q_offsets, const int32_t *widths,
                 const uint8_t *kinds, int nq, int order, int m, hipStream_t st);
+// Where a phrase / proximity pass (sme_phrase_pass.hpp) leaves its results on the
+// index: the output buffers (owned by the index until the feature's next call) and
+// the call's counts.
+struct PassOut {
+  DevBuf &off, &docno, &freq, &score;
+  int64_t &total;
+  uint64_t &cands, &verified, &matches;
+};
+// What narrows a proximity pass (structured queries): pass query i cannot be a
+// result outside any of the groups [qgoff[owner[i]], qgoff[owner[i] + 1]), group g
+// being the union of the posting lists of terms[goff[g] .. goff[g + 1]) (-1: an
+// empty list).  Host arrays; at most kNarrowGroups groups and kNarrowSlots slots
+// per owner (what the filter stages in LDS).
+constexpr int kNarrowGroups = 16, kNarrowSlots = 256;
+struct NarrowSpec {
+  std::vector<int32_t> owner;   // [nq]
+  std::vector<int64_t> qgoff;   // [owners + 1]
+  std::vector<int64_t> goff;    // [groups + 1]
+  std::vector<int32_t> terms;   // [slots]
+};
+// query_near behind its validation: the batch through the pass into `out`, the
+// candidate filter narrowed by `narrow` if given (sme_near.hip)
+void near_pass(sme_index *ix, const PassOut &out, const int32_t *term_ids, const int64_t *q_offsets,
+               const int32_t *widths, const uint8_t *kinds, int nq, int order, int m, const NarrowSpec *narrow,
+               hipStream_t st);
+// structured queries (sme_structq.hip): nq queries of required / excluded groups of
+// leaves -- a term, or an ordered / unordered window over terms (host arrays,
+// validated here) -> per query the matching documents and scores, ordered and cut
+// as query_boolean's: ix->d_sq_off / d_sq_docno / d_sq_score / sq_total, and the
+// call's counts sq_leaves / sq_verified / sq_cands / sq_matches
+void query_structured(sme_index *ix, const int32_t *term_ids, const int64_t *l_offsets, const uint8_t *l_kinds,
+                      const int32_t *l_widths, const int64_t *g_offsets, const uint8_t *g_flags,
+                      const int64_t *q_offsets, int nq, int order, int m, hipStream_t st);
 // The idf of a term with document frequency df among N documents, the one
 // expression behind the build's idf tables (idf_by_df[df] = idf_value(N, df),
 // idf_by_q[q] = idf_value(q, 1) read at q = N / df: log10 of the integer quotient)

@@ -169,7 +169,15 @@ void query_near(sme_index *ix, const int32_t *term_ids, const int64_t *q_offsets
     const bool limit = near::describe(rc, bad, msg, sizeof msg);
     throw Error(limit ? SME_ELIMIT : SME_EINVAL, msg);
   }
-  Blob blob;  // one upload: term offsets | term ids | widths | kinds
+  const PassOut out{ix->d_nq_off, ix->d_nq_docno, ix->d_nq_freq,    ix->d_nq_score,
+                    ix->nq_total, ix->nq_cands,   ix->nq_verified, ix->nq_matches};
+  near_pass(ix, out, term_ids, q_offsets, widths, kinds, nq, order, m, nullptr, st);
+}
+
+void near_pass(sme_index *ix, const PassOut &out, const int32_t *term_ids, const int64_t *q_offsets,
+               const int32_t *widths, const uint8_t *kinds, int nq, int order, int m, const NarrowSpec *narrow,
+               hipStream_t st) {
+  Blob blob;  // one upload: term offsets | term ids | widths | kinds (| the narrowing tables)
   size_t a_poff = 0, a_term = 0, a_width = 0, a_kind = 0;
   // The scorer table: an ordered freq is at most the last term's tf (<= max_tf), an
   // unordered one at most the sum of its distinct terms' tfs, |T| * max_tf -- the
@@ -218,32 +226,50 @@ void query_near(sme_index *ix, const int32_t *term_ids, const int64_t *q_offsets
   DevBuf ovb;
   ovb.pool = &ix->ctx->pool;
   unsigned int *d_over = nullptr;
-  const PassOut out{ix->d_nq_off, ix->d_nq_docno, ix->d_nq_freq,    ix->d_nq_score,
-                    ix->nq_total, ix->nq_cands,   ix->nq_verified, ix->nq_matches};
-  run_pass(
-      ix, out, blob, a_poff, a_term, nq, order, m, "proximity query: 2^31 or more candidate documents in one batch", st,
-      [&](const uint8_t *d_in, Batch b, const int32_t *cdoc, const uint32_t *cph, int64_t C, int32_t *freq,
+  const char *limit = "proximity query: 2^31 or more candidate documents in one batch";
+  const auto verify = [&](const uint8_t *d_in, Batch b, const int32_t *cdoc, const uint32_t *cph, int64_t C, int32_t *freq,
           uint8_t *flag) {
         hipLaunchKernelGGL(k_near_verify, dim3(verify_grid(C)), dim3(kVerifyNT), 0, st, b,
                            (const int32_t *)(d_in + a_width), d_in + a_kind, cdoc, cph, C,
                            (const int64_t *)ix->d_ps_off.p, (const int32_t *)ix->d_ps_terms.p,
                            (const int32_t *)ix->d_ps_docno.p, ix->ps_records, freq, flag);
-      },
-      [&](unsigned g, const int32_t *idx, int64_t T, const int32_t *cdoc, const uint32_t *cph, const int32_t *freq,
+      };
+  const auto score = [&](unsigned g, const int32_t *idx, int64_t T, const int32_t *cdoc, const uint32_t *cph, const int32_t *freq,
           const double *d_idf, int32_t *mdoc, uint32_t *mph, int32_t *mfreq, double *mscore) {
         d_over = ovb.as<unsigned int>(1);
         SME_HIP(hipMemsetAsync(d_over, 0, sizeof(unsigned int), st));
         hipLaunchKernelGGL(k_near_score, dim3(g), dim3(kNT), 0, st, idx, T, cdoc, cph, freq,
                            (const double *)ix->d_nq_lut.p, lut_n, d_idf, mdoc, mph, mfreq, mscore, d_over);
-      });
+      };
+  if (narrow && nq > 0) {
+    // the filter of structured queries: every candidate must also lie in the owner's groups
+    const size_t owners = narrow->qgoff.size() - 1;
+    for (size_t o = 0; o < owners; o++)
+      if (narrow->qgoff[o + 1] - narrow->qgoff[o] > kNarrowGroups ||
+          narrow->goff[(size_t)narrow->qgoff[o + 1]] - narrow->goff[(size_t)narrow->qgoff[o]] > kNarrowSlots)
+        throw Error(SME_EINVAL, "proximity pass: a narrowing spec past what the filter stages");
+    const size_t a_own = blob.add(narrow->owner.data(), narrow->owner.size());
+    const size_t a_qg = blob.add(narrow->qgoff.data(), narrow->qgoff.size());
+    const size_t a_g = blob.add(narrow->goff.data(), narrow->goff.size());
+    const size_t a_nt = blob.add(narrow->terms.data(), narrow->terms.size());
+    run_pass(
+        ix, out, blob, a_poff, a_term, nq, order, m, limit, st,
+        [&](const uint8_t *d_in, const PhraseOp &p) {
+          return NarrowOp{p, (const int32_t *)(d_in + a_own), (const int64_t *)(d_in + a_qg),
+                          (const int64_t *)(d_in + a_g), (const int32_t *)(d_in + a_nt)};
+        },
+        verify, score);
+  } else {
+    run_pass(ix, out, blob, a_poff, a_term, nq, order, m, limit, st, PlainFilter{}, verify, score);
+  }
   if (d_over) {
     unsigned int over = 0;
     SME_HIP(hipMemcpyAsync(&over, d_over, sizeof over, hipMemcpyDeviceToHost, st));
     SME_HIP(hipStreamSynchronize(st));
     if (over) {
-      ix->nq_total = 0;  // the call returns nothing, and its stats say so
-      ix->nq_cands = ix->nq_verified = ix->nq_matches = 0;
-      SME_HIP(hipMemsetAsync(ix->d_nq_off.p, 0, ((size_t)nq + 1) * sizeof(int64_t), st));
+      out.total = 0;  // the call returns nothing, and its stats say so
+      out.cands = out.verified = out.matches = 0;
+      SME_HIP(hipMemsetAsync(out.off.p, 0, ((size_t)nq + 1) * sizeof(int64_t), st));
       SME_HIP(hipStreamSynchronize(st));
       throw Error(SME_ELIMIT, "proximity query: " + std::to_string(over) +
                                   " match(es) with a freq past the scorer table (the index's tfs and its streams disagree)");

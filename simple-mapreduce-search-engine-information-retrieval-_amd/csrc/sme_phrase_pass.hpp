@@ -10,7 +10,10 @@
 // (query, docno) its freq and a flag; the flagged pairs are compacted, scored by
 // the feature's score kernel and, for the score order, sorted by stable passes over
 // an index permutation.  Candidates leave the filter by query and docno ascending,
-// so the docno order needs no sort.  run_pass is that sequence on the host.
+// so the docno order needs no sort.  run_pass is that sequence on the host.  It
+// takes the filter's Op as a parameter: PhraseOp for phrase and proximity calls,
+// NarrowOp -- PhraseOp plus the group test of a structured query's term-only
+// groups -- for the operator leaves of sme_structq.hip.
 //
 // The kernels stand in an unnamed namespace: each of the two files has its own.
 #pragma once
@@ -150,6 +153,76 @@ struct PhraseOp {
     cph[at] = (uint32_t)r;
   }
 };
+// PhraseOp narrowed (structured queries; NarrowSpec in sme_internal.hpp): phrase r
+// belongs to owner[r], whose groups of term slots every result must lie in.  After
+// PhraseOp's staging, per slot of the owner's groups the sub-range of its posting
+// list inside the chunk's docno range is staged once; a group whose sub-ranges are
+// all empty rejects the chunk.  A candidate survives PhraseOp's test and, per
+// group, a search of at least one slot's sub-range (OR over the group's slots).
+// A slot of term -1 and a group without slots hold nothing.
+struct NarrowOp {
+  PhraseOp p;
+  const int32_t *owner;  // [np]
+  const int64_t *qgoff;  // [owners + 1] group offsets
+  const int64_t *goff;   // [groups + 1] slot offsets
+  const int32_t *nterm;  // [slots]
+  struct Lds {
+    PhraseOp::Lds p;
+    int64_t start[kNarrowSlots];
+    int32_t len[kNarrowSlots];
+    int32_t gbeg[kNarrowGroups + 1];
+    int reject;
+  };
+  struct Chunk {
+    PhraseOp::Chunk p;
+    int ng;
+  };
+  using Cand = PhraseOp::Cand;
+  __device__ __forceinline__ bool stage(Lds &s, Chunk &k, int64_t r, int64_t c0, int len) const {
+    if (!p.stage(s.p, k.p, r, c0, len)) return false;  // (the same verdict in every thread)
+    const int tid = threadIdx.x;
+    const int o = owner[r];
+    const int64_t g0 = qgoff[o];
+    k.ng = (int)(qgoff[o + 1] - g0);  // <= kNarrowGroups (the host cuts the spec)
+    if (k.ng == 0) return true;
+    const int64_t s0 = goff[g0];
+    const int S = (int)(goff[g0 + k.ng] - s0);  // <= kNarrowSlots
+    const int32_t first = p.docno[k.p.base + c0], last = p.docno[k.p.base + c0 + len - 1];
+    if (tid <= k.ng) s.gbeg[tid] = (int32_t)(goff[g0 + tid] - s0);
+    if (tid == 0) s.reject = 0;
+    for (int j = tid; j < S; j += kNT) {
+      const int32_t t = nterm[s0 + j];
+      const int64_t beg = t < 0 ? 0 : p.doff[t];
+      const int n = t < 0 ? 0 : (int)(p.doff[t + 1] - beg);
+      const int lo = lower_bound(p.docno + beg, n, first);
+      const int hi = lo + upper_bound(p.docno + beg + lo, n - lo, last);
+      s.start[j] = beg + lo;
+      s.len[j] = hi - lo;
+    }
+    __syncthreads();
+    if (tid < k.ng) {
+      int any = 0;
+      for (int j = s.gbeg[tid]; j < s.gbeg[tid + 1]; j++) any |= s.len[j];
+      if (any == 0) s.reject = 1;
+    }
+    __syncthreads();
+    return s.reject == 0;
+  }
+  __device__ __forceinline__ bool test(const Lds &s, const Chunk &k, int64_t r, int64_t c, Cand &x) const {
+    bool hit = p.test(s.p, k.p, r, c, x);
+    for (int g = 0; hit && g < k.ng; g++) {
+      bool held = false;
+      for (int j = s.gbeg[g]; !held && j < s.gbeg[g + 1]; j++)
+        held = find_doc(p.docno, s.start[j], s.len[j], x.d) >= 0;
+      hit = held;
+    }
+    return hit;
+  }
+  __device__ __forceinline__ void emit(const Lds &s, const Chunk &k, int64_t r, const Cand &x, int64_t at,
+                                       int32_t *__restrict__ cdoc, uint32_t *__restrict__ cph) const {
+    p.emit(s.p, k.p, r, x, at, cdoc, cph);
+  }
+};
 struct SelfRange {  // phrase i owns range i
   __device__ int64_t operator()(int64_t i) const { return i; }
 };
@@ -217,25 +290,23 @@ __global__ void k_phrase_gather(const uint32_t *__restrict__ qs, const uint32_t 
   }
 }
 
-// Where a pass leaves its results on the index: the output buffers (owned by the
-// index until the feature's next call) and the call's counts.
-struct PassOut {
-  DevBuf &off, &docno, &freq, &score;
-  int64_t &total;
-  uint64_t &cands, &verified, &matches;
+struct PlainFilter {  // run_pass's make_op of a pass that filters by the phrase's own terms alone
+  PhraseOp operator()(const uint8_t *, const PhraseOp &p) const { return p; }
 };
 
-// One pass over a validated batch of np queries: `blob` is the upload, holding the
-// term offsets at a_poff and the term ids at a_term beside whatever else the
-// feature's verify kernel reads.
+// One pass over a validated batch of np queries into `out` (PassOut,
+// sme_internal.hpp): `blob` is the upload, holding the term offsets at a_poff and
+// the term ids at a_term beside whatever else the feature's kernels read.
+//   make_op(d_in, phrase_op)  the chunk filter's Op: PhraseOp itself (PlainFilter),
+//       or one that tests more on top of it (d_in: the uploaded blob)
 //   verify(d_in, b, cdoc, cph, C, freq, flag)  launches the verify kernel over the
 //       C candidates: freq[x] and flag[x] = freq[x] > 0 (d_in: the uploaded blob)
 //   score(grid, idx, T, cdoc, cph, freq, d_idf, mdoc, mph, mfreq, mscore)  launches
 //       the score kernel over the T matches
 // `limit` is the SME_ELIMIT message at 2^31 candidates or more.
-template <class Verify, class Score>
+template <class MakeOp, class Verify, class Score>
 void run_pass(sme_index *ix, const PassOut &out, const Blob &blob, size_t a_poff, size_t a_term, int np, int order,
-              int m, const char *limit, hipStream_t st, Verify verify, Score score) {
+              int m, const char *limit, hipStream_t st, MakeOp make_op, Verify verify, Score score) {
   sme_ctx *cx = ix->ctx;
   out.total = 0;
   out.cands = 0;
@@ -272,7 +343,7 @@ void run_pass(sme_index *ix, const PassOut &out, const Blob &blob, size_t a_poff
                        dpos, choff, d_cands);
     SME_CHECK_LAUNCH();
     unsigned long long cands = 0;
-    const PhraseOp op{b, dbeg, dpos, doff, docno};
+    const auto op = make_op(d_in, PhraseOp{b, dbeg, dpos, doff, docno});
     const Counted c = count_chunks(op, np, choff, dcnt, chunk, mob, scn, limit, st, d_cands, &cands);
     const int64_t C = c.total;  // (phrase, docno) pairs that hold all the phrase's terms
     int64_t T = 0, out_total = 0;
