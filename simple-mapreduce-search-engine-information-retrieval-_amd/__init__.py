@@ -530,44 +530,98 @@ class Index:
         _check(lib().sme_index_prepare_wildcards(self._h, C.c_void_p(stream or 0), C.byref(ms)))
         return ms.value
 
+    # ---- the batched query features: n queries in, n + 1 offsets and one to three
+    # value columns out (include/sme.h).  The four patterns below are each written
+    # once; a feature names its entry, its input dtypes and its column dtypes.
+    _CT = {np.int32: C.c_int32, np.int64: C.c_int64, np.uint8: C.c_uint8, np.float64: C.c_double}
+
+    @staticmethod
+    def _typed_ptrs(arrays, dtypes):
+        """(the arrays to keep alive, their ctypes pointers): contiguous, of the
+        given dtypes, and never empty (an empty numpy array may hand out any
+        pointer: one element is kept behind each)."""
+        keep, ptrs = [], []
+        for a, dt in zip(arrays, dtypes):
+            a = np.ascontiguousarray(a, dtype=dt)
+            a = a if a.size else np.zeros(1, dt)
+            keep.append(a)
+            ptrs.append(a.ctypes.data_as(C.POINTER(Index._CT[dt])))
+        return keep, ptrs
+
+    @staticmethod
+    def _host_call(h, fn, args, n, cols):
+        """fn(index, *args, &offsets, &column...) -> (offsets int64[n+1], one array
+        per dtype of cols), copied at once: the library's arrays are the index's
+        until the feature's next call.  An empty column is np.zeros(0, dt)."""
+        outs = [C.POINTER(Index._CT[dt])() for dt in (np.int64,) + cols]
+        _check(fn(h, *args, *[C.byref(o) for o in outs]))
+        off = np.ctypeslib.as_array(outs[0], (n + 1,)).copy()
+        total = int(off[n])
+        return (off,) + tuple(np.ctypeslib.as_array(o, (total,)).copy() if total else np.zeros(0, dt)
+                              for o, dt in zip(outs[1:], cols))
+
+    @staticmethod
+    def _device_call(h, fn, args, stream, cols):
+        """fn(index, *args, stream, &offsets, &column..., &total) -> (device pointer
+        of the offsets, of every column, total); a NULL pointer is 0."""
+        outs = [C.c_void_p() for _ in range(len(cols) + 1)]
+        tot = C.c_int64()
+        _check(fn(h, *args, C.c_void_p(stream or 0), *[C.byref(o) for o in outs], C.byref(tot)))
+        return tuple(o.value or 0 for o in outs) + (tot.value,)
+
+    @staticmethod
+    def _query_host(h, fn, arrays, dtypes, nq, order, m, cols):
+        """_host_call over a batch of nq queries given as its arrays."""
+        keep, ptrs = Index._typed_ptrs(arrays, dtypes)
+        return Index._host_call(h, fn, ptrs + [nq, int(order), int(m)], nq, cols)
+
+    @staticmethod
+    def _query_device(h, fn, arrays, dtypes, nq, order, m, stream, cols):
+        """_device_call over a batch of nq queries given as its arrays."""
+        keep, ptrs = Index._typed_ptrs(arrays, dtypes)
+        return Index._device_call(h, fn, ptrs + [nq, int(order), int(m)], stream, cols)
+
+    @staticmethod
+    def _stats(h, fn, count):
+        """fn(index, &uint64...) -> the `count` values."""
+        vals = [C.c_uint64() for _ in range(count)]
+        _check(fn(h, *[C.byref(v) for v in vals]))
+        return tuple(v.value for v in vals)
+
+    _TERM_COLS, _SUGGEST_COLS = (np.int32,), (np.int32, np.uint8)
+    _DOC_COLS, _PASS_COLS = (np.int32, np.float64), (np.int32, np.int32, np.float64)
+    _BOOLEAN_IN = (np.int32, np.int64, np.uint8, np.int64)
+    _PHRASE_IN = (np.int32, np.int64)
+    _NEAR_IN = (np.int32, np.int64, np.int32, np.uint8)
+    _STRUCTURED_IN = (np.int32, np.int64, np.uint8, np.int32, np.int64, np.uint8, np.int64)
+
     def wildcard_stats(self):
         """(distinct trigram keys, distinct (key, term) pairs) of the wildcard table."""
-        a, b = C.c_uint64(), C.c_uint64()
-        _check(lib().sme_index_wildcard_stats(self._h, C.byref(a), C.byref(b)))
-        return a.value, b.value
+        return Index._stats(self._h, lib().sme_index_wildcard_stats, 2)
 
     @staticmethod
     def _pattern_args(patterns):
+        """(the offsets array to keep alive, (blob, offsets pointer, n)) of str / bytes patterns."""
         bs = [p if isinstance(p, (bytes, bytearray)) else p.encode("utf-8", "surrogatepass") for p in patterns]
         offs = np.zeros(len(bs) + 1, dtype=np.int64)
         if bs:
             offs[1:] = np.cumsum([len(b) for b in bs])
-        return b"".join(bs), offs, len(bs)
+        return offs, (b"".join(bs), offs.ctypes.data_as(C.POINTER(C.c_int64)), len(bs))
 
     def expand_wildcards(self, patterns):
         """sme_index_expand_wildcards: patterns (str, or bytes of UTF-8) -> (match_off
         int64[n+1], term_ids int32); pattern i matches term_ids[match_off[i]:
         match_off[i+1]], ascending.  '*' = any run of UTF-16 units, '?' = one unit;
         no case folding (include/sme.h)."""
-        blob, offs, n = Index._pattern_args(patterns)
-        mo, ti = C.POINTER(C.c_int64)(), C.POINTER(C.c_int32)()
-        _check(lib().sme_index_expand_wildcards(self._h, blob, offs.ctypes.data_as(C.POINTER(C.c_int64)), n,
-                                                C.byref(mo), C.byref(ti)))
-        off = np.ctypeslib.as_array(mo, (n + 1,)).copy()
-        total = int(off[n])
-        ids = np.ctypeslib.as_array(ti, (total,)).copy() if total else np.zeros(0, np.int32)
-        return off, ids
+        keep, args = Index._pattern_args(patterns)
+        return Index._host_call(self._h, lib().sme_index_expand_wildcards, args, args[2], Index._TERM_COLS)
 
     def expand_wildcards_device(self, patterns, stream=None):
         """sme_index_expand_wildcards_device: (device pointer of match_off int64[n+1],
         device pointer of term_ids int32[total], total); the arrays belong to the
         index until its next expansion."""
-        blob, offs, n = Index._pattern_args(patterns)
-        mo, ti, tot = C.c_void_p(), C.c_void_p(), C.c_int64()
-        _check(lib().sme_index_expand_wildcards_device(self._h, blob, offs.ctypes.data_as(C.POINTER(C.c_int64)), n,
-                                                       C.c_void_p(stream or 0), C.byref(mo), C.byref(ti),
-                                                       C.byref(tot)))
-        return mo.value or 0, ti.value or 0, tot.value
+        keep, args = Index._pattern_args(patterns)
+        return Index._device_call(self._h, lib().sme_index_expand_wildcards_device, args, stream, Index._TERM_COLS)
 
     def suggest_terms(self, words, max_dist=2, m=10):
         """sme_index_suggest_terms: words (str, or bytes of UTF-8) -> (sug_off
@@ -575,34 +629,23 @@ class Index:
         term_ids[sug_off[i]:sug_off[i+1]], the terms within max_dist (0..3) unit
         edits of it ordered by (distance asc, df desc, term id asc) and cut to the
         first m (0: no cut); dist runs parallel to term_ids (include/sme.h)."""
-        blob, offs, n = Index._pattern_args(words)
-        so, ti, di = C.POINTER(C.c_int64)(), C.POINTER(C.c_int32)(), C.POINTER(C.c_uint8)()
-        _check(lib().sme_index_suggest_terms(self._h, blob, offs.ctypes.data_as(C.POINTER(C.c_int64)), n,
-                                             int(max_dist), int(m), C.byref(so), C.byref(ti), C.byref(di)))
-        off = np.ctypeslib.as_array(so, (n + 1,)).copy()
-        total = int(off[n])
-        ids = np.ctypeslib.as_array(ti, (total,)).copy() if total else np.zeros(0, np.int32)
-        dist = np.ctypeslib.as_array(di, (total,)).copy() if total else np.zeros(0, np.uint8)
-        return off, ids, dist
+        keep, args = Index._pattern_args(words)
+        return Index._host_call(self._h, lib().sme_index_suggest_terms, args + (int(max_dist), int(m)), args[2],
+                               Index._SUGGEST_COLS)
 
     def suggest_terms_device(self, words, max_dist=2, m=10, stream=None):
         """sme_index_suggest_terms_device: (device pointer of sug_off int64[n+1],
         of term_ids int32[total], of dist uint8[total], total); the arrays belong
         to the index until its next suggestion call."""
-        blob, offs, n = Index._pattern_args(words)
-        so, ti, di, tot = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int64()
-        _check(lib().sme_index_suggest_terms_device(self._h, blob, offs.ctypes.data_as(C.POINTER(C.c_int64)), n,
-                                                    int(max_dist), int(m), C.c_void_p(stream or 0), C.byref(so),
-                                                    C.byref(ti), C.byref(di), C.byref(tot)))
-        return so.value or 0, ti.value or 0, di.value or 0, tot.value
+        keep, args = Index._pattern_args(words)
+        return Index._device_call(self._h, lib().sme_index_suggest_terms_device, args + (int(max_dist), int(m)), stream,
+                                 Index._SUGGEST_COLS)
 
     def suggest_stats(self):
         """(scanned_words, candidates) of the last suggestion call: the words that
         took the whole vocabulary as candidates, and the (word, term) pairs that
         reached the length test."""
-        a, b = C.c_uint64(), C.c_uint64()
-        _check(lib().sme_index_suggest_stats(self._h, C.byref(a), C.byref(b)))
-        return a.value, b.value
+        return Index._stats(self._h, lib().sme_index_suggest_stats, 2)
 
     @staticmethod
     def boolean_arrays(queries):
@@ -619,17 +662,6 @@ class Index:
         return (np.array(terms, np.int32), np.array(goff, np.int64), np.array(flags, np.uint8),
                 np.array(qoff, np.int64))
 
-    @staticmethod
-    def _boolean_ptrs(term_ids, g_offsets, g_flags, q_offsets):
-        # (an empty numpy array may hand out any pointer: keep one element behind each)
-        arrs = []
-        for a, dt in ((term_ids, np.int32), (g_offsets, np.int64), (g_flags, np.uint8), (q_offsets, np.int64)):
-            a = np.ascontiguousarray(a, dtype=dt)
-            arrs.append(a if a.size else np.zeros(1, dt))
-        t, g, f, q = arrs
-        return arrs, (t.ctypes.data_as(C.POINTER(C.c_int32)), g.ctypes.data_as(C.POINTER(C.c_int64)),
-                      f.ctypes.data_as(C.POINTER(C.c_uint8)), q.ctypes.data_as(C.POINTER(C.c_int64)))
-
     def query_boolean(self, queries, order=0, m=0, arrays=None):
         """sme_query_boolean: queries = a list of queries, each a list of
         (term_ids, excluded) groups -- a document matches when it lies in at least
@@ -640,34 +672,22 @@ class Index:
         ordered by docno ascending (order 0) or score descending then docno
         ascending (order 1) and cut to the first m (0: no cut) (include/sme.h).
         arrays: the structure as boolean_arrays returns it, instead of queries."""
-        t, g, f, q = arrays if arrays is not None else Index.boolean_arrays(queries)
-        nq = len(q) - 1
-        keep, ptrs = Index._boolean_ptrs(t, g, f, q)
-        ro, dn, sc = C.POINTER(C.c_int64)(), C.POINTER(C.c_int32)(), C.POINTER(C.c_double)()
-        _check(lib().sme_query_boolean(self._h, *ptrs, nq, int(order), int(m), C.byref(ro), C.byref(dn), C.byref(sc)))
-        off = np.ctypeslib.as_array(ro, (nq + 1,)).copy()
-        total = int(off[nq])
-        docno = np.ctypeslib.as_array(dn, (total,)).copy() if total else np.zeros(0, np.int32)
-        score = np.ctypeslib.as_array(sc, (total,)).copy() if total else np.zeros(0, np.float64)
-        return off, docno, score
+        a = arrays if arrays is not None else Index.boolean_arrays(queries)
+        return Index._query_host(self._h, lib().sme_query_boolean, a, Index._BOOLEAN_IN, len(a[3]) - 1,
+                                 order, m, Index._DOC_COLS)
 
     def query_boolean_device(self, queries, order=0, m=0, stream=None, arrays=None):
         """sme_query_boolean_device: (device pointer of res_off int64[nq+1], of
         docno int32[total], of score float64[total], total); the arrays belong to
         the index until its next Boolean call."""
-        t, g, f, q = arrays if arrays is not None else Index.boolean_arrays(queries)
-        keep, ptrs = Index._boolean_ptrs(t, g, f, q)
-        ro, dn, sc, tot = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int64()
-        _check(lib().sme_query_boolean_device(self._h, *ptrs, len(q) - 1, int(order), int(m), C.c_void_p(stream or 0),
-                                              C.byref(ro), C.byref(dn), C.byref(sc), C.byref(tot)))
-        return ro.value or 0, dn.value or 0, sc.value or 0, tot.value
+        a = arrays if arrays is not None else Index.boolean_arrays(queries)
+        return Index._query_device(self._h, lib().sme_query_boolean_device, a, Index._BOOLEAN_IN, len(a[3]) - 1,
+                                   order, m, stream, Index._DOC_COLS)
 
     def boolean_stats(self):
         """(candidates, matches) of the last Boolean call: the driver postings
         examined, and the matches before the cut."""
-        a, b = C.c_uint64(), C.c_uint64()
-        _check(lib().sme_query_boolean_stats(self._h, C.byref(a), C.byref(b)))
-        return a.value, b.value
+        return Index._stats(self._h, lib().sme_query_boolean_stats, 2)
 
     def positions(self):
         """sme_index_positions: (records, positions, bytes) of the term streams the
@@ -687,15 +707,6 @@ class Index:
             poff.append(len(terms))
         return np.array(terms, np.int32), np.array(poff, np.int64)
 
-    @staticmethod
-    def _phrase_ptrs(term_ids, p_offsets):
-        # (an empty numpy array may hand out any pointer: keep one element behind each)
-        t = np.ascontiguousarray(term_ids, dtype=np.int32)
-        o = np.ascontiguousarray(p_offsets, dtype=np.int64)
-        t = t if t.size else np.zeros(1, np.int32)
-        o = o if o.size else np.zeros(1, np.int64)
-        return (t, o), (t.ctypes.data_as(C.POINTER(C.c_int32)), o.ctypes.data_as(C.POINTER(C.c_int64)))
-
     def query_phrase(self, phrases, order=0, m=0, arrays=None):
         """sme_query_phrase: phrases = a list of phrases, each a list of term ids
         (Index.lookup's; -1 = unknown, the phrase then has no result).  A document
@@ -708,37 +719,23 @@ class Index:
         descending then docno ascending (order 1), cut to the first m (0: no cut)
         (include/sme.h).  The index must keep positions (Index.positions).
         arrays: the structure as phrase_arrays returns it, instead of phrases."""
-        t, o = arrays if arrays is not None else Index.phrase_arrays(phrases)
-        n = len(o) - 1
-        keep, ptrs = Index._phrase_ptrs(t, o)
-        ro, dn, fq, sc = C.POINTER(C.c_int64)(), C.POINTER(C.c_int32)(), C.POINTER(C.c_int32)(), C.POINTER(C.c_double)()
-        _check(lib().sme_query_phrase(self._h, *ptrs, n, int(order), int(m), C.byref(ro), C.byref(dn), C.byref(fq),
-                                      C.byref(sc)))
-        off = np.ctypeslib.as_array(ro, (n + 1,)).copy()
-        total = int(off[n])
-        docno = np.ctypeslib.as_array(dn, (total,)).copy() if total else np.zeros(0, np.int32)
-        freq = np.ctypeslib.as_array(fq, (total,)).copy() if total else np.zeros(0, np.int32)
-        score = np.ctypeslib.as_array(sc, (total,)).copy() if total else np.zeros(0, np.float64)
-        return off, docno, freq, score
+        a = arrays if arrays is not None else Index.phrase_arrays(phrases)
+        return Index._query_host(self._h, lib().sme_query_phrase, a, Index._PHRASE_IN, len(a[1]) - 1,
+                                 order, m, Index._PASS_COLS)
 
     def query_phrase_device(self, phrases, order=0, m=0, stream=None, arrays=None):
         """sme_query_phrase_device: (device pointer of res_off int64[np+1], of docno
         int32[total], of freq int32[total], of score float64[total], total); the
         arrays belong to the index until its next phrase call."""
-        t, o = arrays if arrays is not None else Index.phrase_arrays(phrases)
-        keep, ptrs = Index._phrase_ptrs(t, o)
-        ro, dn, fq, sc, tot = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int64()
-        _check(lib().sme_query_phrase_device(self._h, *ptrs, len(o) - 1, int(order), int(m), C.c_void_p(stream or 0),
-                                             C.byref(ro), C.byref(dn), C.byref(fq), C.byref(sc), C.byref(tot)))
-        return ro.value or 0, dn.value or 0, fq.value or 0, sc.value or 0, tot.value
+        a = arrays if arrays is not None else Index.phrase_arrays(phrases)
+        return Index._query_device(self._h, lib().sme_query_phrase_device, a, Index._PHRASE_IN, len(a[1]) - 1,
+                                   order, m, stream, Index._PASS_COLS)
 
     def phrase_stats(self):
         """(candidates, verified, matches) of the last phrase call: the driver
         postings examined, the (phrase, document) pairs whose records were
         scanned, and the matches before the cut."""
-        a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
-        _check(lib().sme_query_phrase_stats(self._h, C.byref(a), C.byref(b), C.byref(c)))
-        return a.value, b.value, c.value
+        return Index._stats(self._h, lib().sme_query_phrase_stats, 3)
 
     @staticmethod
     def near_arrays(queries):
@@ -754,15 +751,6 @@ class Index:
         return (np.array(terms, np.int32), np.array(qoff, np.int64), np.array(widths, np.int32),
                 np.array(kinds, np.uint8))
 
-    @staticmethod
-    def _near_ptrs(term_ids, q_offsets, widths, kinds):
-        (t, o), ptrs = Index._phrase_ptrs(term_ids, q_offsets)
-        w = np.ascontiguousarray(widths, dtype=np.int32)
-        k = np.ascontiguousarray(kinds, dtype=np.uint8)
-        w = w if w.size else np.zeros(1, np.int32)
-        k = k if k.size else np.zeros(1, np.uint8)
-        return (t, o, w, k), ptrs + (w.ctypes.data_as(C.POINTER(C.c_int32)), k.ctypes.data_as(C.POINTER(C.c_uint8)))
-
     def query_near(self, queries, order=0, m=0, arrays=None):
         """sme_query_near: queries = a list of (term_ids, width, ordered), the ids
         Index.lookup's (-1 = unknown, the query then has no result), at most 32.
@@ -777,36 +765,22 @@ class Index:
         The index must keep positions (Index.positions).
         arrays: the structure as near_arrays returns it, instead of queries."""
         a = arrays if arrays is not None else Index.near_arrays(queries)
-        n = len(a[1]) - 1
-        keep, ptrs = Index._near_ptrs(*a)
-        ro, dn, fq, sc = C.POINTER(C.c_int64)(), C.POINTER(C.c_int32)(), C.POINTER(C.c_int32)(), C.POINTER(C.c_double)()
-        _check(lib().sme_query_near(self._h, *ptrs, n, int(order), int(m), C.byref(ro), C.byref(dn), C.byref(fq),
-                                    C.byref(sc)))
-        off = np.ctypeslib.as_array(ro, (n + 1,)).copy()
-        total = int(off[n])
-        docno = np.ctypeslib.as_array(dn, (total,)).copy() if total else np.zeros(0, np.int32)
-        freq = np.ctypeslib.as_array(fq, (total,)).copy() if total else np.zeros(0, np.int32)
-        score = np.ctypeslib.as_array(sc, (total,)).copy() if total else np.zeros(0, np.float64)
-        return off, docno, freq, score
+        return Index._query_host(self._h, lib().sme_query_near, a, Index._NEAR_IN, len(a[1]) - 1,
+                                 order, m, Index._PASS_COLS)
 
     def query_near_device(self, queries, order=0, m=0, stream=None, arrays=None):
         """sme_query_near_device: (device pointer of res_off int64[nq+1], of docno
         int32[total], of freq int32[total], of score float64[total], total); the
         arrays belong to the index until its next proximity call."""
         a = arrays if arrays is not None else Index.near_arrays(queries)
-        keep, ptrs = Index._near_ptrs(*a)
-        ro, dn, fq, sc, tot = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int64()
-        _check(lib().sme_query_near_device(self._h, *ptrs, len(a[1]) - 1, int(order), int(m), C.c_void_p(stream or 0),
-                                           C.byref(ro), C.byref(dn), C.byref(fq), C.byref(sc), C.byref(tot)))
-        return ro.value or 0, dn.value or 0, fq.value or 0, sc.value or 0, tot.value
+        return Index._query_device(self._h, lib().sme_query_near_device, a, Index._NEAR_IN, len(a[1]) - 1,
+                                   order, m, stream, Index._PASS_COLS)
 
     def near_stats(self):
         """(candidates, verified, matches) of the last proximity call: the driver
         postings examined, the (query, document) pairs whose records were
         scanned, and the matches before the cut."""
-        a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
-        _check(lib().sme_query_near_stats(self._h, C.byref(a), C.byref(b), C.byref(c)))
-        return a.value, b.value, c.value
+        return Index._stats(self._h, lib().sme_query_near_stats, 3)
 
     @staticmethod
     def structured_arrays(queries):
@@ -831,18 +805,6 @@ class Index:
                 np.array(widths, np.int32), np.array(goff, np.int64), np.array(flags, np.uint8),
                 np.array(qoff, np.int64))
 
-    @staticmethod
-    def _structured_ptrs(arrays):
-        # (an empty numpy array may hand out any pointer: keep one element behind each)
-        keep, ptrs = [], []
-        for a, dt, ct in zip(arrays, (np.int32, np.int64, np.uint8, np.int32, np.int64, np.uint8, np.int64),
-                             (C.c_int32, C.c_int64, C.c_uint8, C.c_int32, C.c_int64, C.c_uint8, C.c_int64)):
-            a = np.ascontiguousarray(a, dtype=dt)
-            a = a if a.size else np.zeros(1, dt)
-            keep.append(a)
-            ptrs.append(a.ctypes.data_as(C.POINTER(ct)))
-        return keep, ptrs
-
     def query_structured(self, queries, order=0, m=0, arrays=None):
         """sme_query_structured: queries = a list of queries, each a list of
         (leaves, excluded) groups; a leaf is (term_ids, kind, width): kind 0 a term
@@ -857,37 +819,23 @@ class Index:
         index that keeps positions (Index.positions).
         arrays: the structure as structured_arrays returns it, instead of queries."""
         a = arrays if arrays is not None else Index.structured_arrays(queries)
-        nq = len(a[6]) - 1
-        keep, ptrs = Index._structured_ptrs(a)
-        ro, dn, sc = C.POINTER(C.c_int64)(), C.POINTER(C.c_int32)(), C.POINTER(C.c_double)()
-        _check(lib().sme_query_structured(self._h, *ptrs, nq, int(order), int(m), C.byref(ro), C.byref(dn),
-                                          C.byref(sc)))
-        off = np.ctypeslib.as_array(ro, (nq + 1,)).copy()
-        total = int(off[nq])
-        docno = np.ctypeslib.as_array(dn, (total,)).copy() if total else np.zeros(0, np.int32)
-        score = np.ctypeslib.as_array(sc, (total,)).copy() if total else np.zeros(0, np.float64)
-        return off, docno, score
+        return Index._query_host(self._h, lib().sme_query_structured, a, Index._STRUCTURED_IN, len(a[6]) - 1,
+                                 order, m, Index._DOC_COLS)
 
     def query_structured_device(self, queries, order=0, m=0, stream=None, arrays=None):
         """sme_query_structured_device: (device pointer of res_off int64[nq+1], of
         docno int32[total], of score float64[total], total); the arrays belong to
         the index until its next structured call."""
         a = arrays if arrays is not None else Index.structured_arrays(queries)
-        keep, ptrs = Index._structured_ptrs(a)
-        ro, dn, sc, tot = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int64()
-        _check(lib().sme_query_structured_device(self._h, *ptrs, len(a[6]) - 1, int(order), int(m),
-                                                 C.c_void_p(stream or 0), C.byref(ro), C.byref(dn), C.byref(sc),
-                                                 C.byref(tot)))
-        return ro.value or 0, dn.value or 0, sc.value or 0, tot.value
+        return Index._query_device(self._h, lib().sme_query_structured_device, a, Index._STRUCTURED_IN, len(a[6]) - 1,
+                                   order, m, stream, Index._DOC_COLS)
 
     def structured_stats(self):
         """(leaves, verified, candidates, matches) of the last structured call: the
         operator leaves evaluated, the (leaf, document) pairs whose records were
         scanned, the Boolean stage's driver entries examined, and the matches
         before the cut."""
-        a, b, c, d = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
-        _check(lib().sme_query_structured_stats(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
-        return a.value, b.value, c.value, d.value
+        return Index._stats(self._h, lib().sme_query_structured_stats, 4)
 
     def reweight(self, n_global, d_df_global=None, stream=None):
         """TF-IDF weights with all-reduced N (and df) of a doc-sharded index."""

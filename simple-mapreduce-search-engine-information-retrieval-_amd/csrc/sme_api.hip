@@ -721,12 +721,38 @@ int sme_lookup_terms(sme_index *ix, const uint8_t *terms, const int64_t *offs, i
   });
 }
 
-// wildcard expansion runs over the vocabulary of a K = 1 term index
-static void need_wildcard_index(const sme_index *ix) {
-  if (ix->job != 0) throw sme::Error(SME_EINVAL, "wildcards: a CharKGramTermIndexer output has no term vocabulary");
+// ---- the batched query features ---------------------------------------------
+// Each leaves a sme::ResultSet on the index (sme_result.hpp).  A _device entry
+// hands out its device arrays, a host entry fetches them into its mirrors and
+// hands those out; either way the arrays are the index's until the same feature's
+// next call.
+void sme::ResultSet::fetch(hipStream_t st) {
+  const size_t tot = (size_t)total;
+  h_off.resize((size_t)n + 1);
+  for (Column &c : col) c.h.resize((tot + 1) * c.esize);  // (never an empty vector: data() stays a valid pointer)
+  SME_HIP(hipMemcpyAsync(h_off.data(), off.p, ((size_t)n + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  if (tot)
+    for (Column &c : col)
+      if (c.esize) SME_HIP(hipMemcpyAsync(c.h.data(), c.d.p, tot * c.esize, hipMemcpyDeviceToHost, st));
+  SME_HIP(hipStreamSynchronize(st));
+}
+
+// a batch of n UTF-8 strings: text may be NULL only while every string is empty
+static bool bad_text_batch(const sme_index *ix, const uint8_t *text, const int64_t *offs, int n) {
+  return !ix || n < 0 || (n > 0 && !offs) || (n > 0 && !text && offs[n] > offs[0]);
+}
+
+// wildcard expansion and spelling suggestions run over the vocabulary of a K = 1
+// term index (`shards`: what the feature tells the holder of merged pieces to do)
+static void need_vocabulary(const sme_index *ix, const std::string &what, const char *shards) {
+  if (ix->job != 0) throw sme::Error(SME_EINVAL, what + ": a CharKGramTermIndexer output has no term vocabulary");
   if (ix->records_only)
-    throw sme::Error(SME_EINVAL, "wildcards: records-only index (merged shard pieces): expand on the shard indexes");
-  if (ix->K != 1) throw sme::Error(SME_EINVAL, "wildcards: K = " + std::to_string(ix->K) + " index (K = 1 only)");
+    throw sme::Error(SME_EINVAL, what + ": records-only index (merged shard pieces): " + shards);
+  if (ix->K != 1) throw sme::Error(SME_EINVAL, what + ": K = " + std::to_string(ix->K) + " index (K = 1 only)");
+}
+
+static void need_wildcard_index(const sme_index *ix) {
+  need_vocabulary(ix, "wildcards", "expand on the shard indexes");
 }
 
 int sme_index_prepare_wildcards(sme_index *ix, void *stream, float *ms) {
@@ -753,50 +779,39 @@ int sme_index_wildcard_stats(sme_index *ix, uint64_t *ngrams, uint64_t *npairs) 
 int sme_index_expand_wildcards_device(sme_index *ix, const uint8_t *patterns, const int64_t *offs, int n, void *stream,
                                       const int64_t **d_match_off, const int32_t **d_term_ids, int64_t *total) {
   return guard([&] {
-    if (!ix || !d_match_off || !d_term_ids || n < 0 || (n > 0 && !offs) || (n > 0 && !patterns && offs[n] > offs[0]))
+    if (!d_match_off || !d_term_ids || bad_text_batch(ix, patterns, offs, n))
       throw sme::Error(SME_EINVAL, "bad argument");
     need_wildcard_index(ix);
     set_device(ix->ctx);
     sme::expand_wildcards(ix, patterns, offs, n, stream_of(ix->ctx, stream));
-    *d_match_off = (const int64_t *)ix->d_wx_off.p;
-    *d_term_ids = (const int32_t *)ix->d_wx_ids.p;
-    if (total) *total = ix->wx_total;
+    const sme::TermIds &r = ix->wx;
+    *d_match_off = r.dev_offsets();
+    *d_term_ids = r.dev<sme::TermIds::ids>();
+    if (total) *total = r.total;
   });
 }
 
 int sme_index_expand_wildcards(sme_index *ix, const uint8_t *patterns, const int64_t *offs, int n,
                                const int64_t **match_off, const int32_t **term_ids) {
   return guard([&] {
-    if (!ix || !match_off || !term_ids || n < 0 || (n > 0 && !offs) || (n > 0 && !patterns && offs[n] > offs[0]))
-      throw sme::Error(SME_EINVAL, "bad argument");
+    if (!match_off || !term_ids || bad_text_batch(ix, patterns, offs, n)) throw sme::Error(SME_EINVAL, "bad argument");
     need_wildcard_index(ix);
     set_device(ix->ctx);
     hipStream_t st = ix->ctx->own_stream;
     sme::expand_wildcards(ix, patterns, offs, n, st);
-    ix->h_wx_off.resize((size_t)n + 1);
-    ix->h_wx_ids.resize((size_t)ix->wx_total + 1);  // (never an empty vector: data() stays a valid pointer)
-    SME_HIP(hipMemcpyAsync(ix->h_wx_off.data(), ix->d_wx_off.p, ((size_t)n + 1) * sizeof(int64_t),
-                           hipMemcpyDeviceToHost, st));
-    if (ix->wx_total)
-      SME_HIP(hipMemcpyAsync(ix->h_wx_ids.data(), ix->d_wx_ids.p, (size_t)ix->wx_total * sizeof(int32_t),
-                             hipMemcpyDeviceToHost, st));
-    SME_HIP(hipStreamSynchronize(st));
-    *match_off = ix->h_wx_off.data();
-    *term_ids = ix->h_wx_ids.data();
+    sme::TermIds &r = ix->wx;
+    r.fetch(st);
+    *match_off = r.h_off.data();
+    *term_ids = r.host<sme::TermIds::ids>();
   });
 }
 
-// spelling suggestions run over the same vocabulary, with the same refusals
 static void need_suggest_args(const sme_index *ix, const uint8_t *words, const int64_t *offs, int n, int max_dist,
                               int m) {
-  if (!ix || n < 0 || (n > 0 && !offs) || (n > 0 && !words && offs[n] > offs[0]))
-    throw sme::Error(SME_EINVAL, "bad argument");
+  if (bad_text_batch(ix, words, offs, n)) throw sme::Error(SME_EINVAL, "bad argument");
   if (max_dist < 0 || max_dist > 3) throw sme::Error(SME_EINVAL, "suggestions: max_dist must be 0..3");
   if (m < 0) throw sme::Error(SME_EINVAL, "suggestions: m must be >= 0");
-  if (ix->job != 0) throw sme::Error(SME_EINVAL, "suggestions: a CharKGramTermIndexer output has no term vocabulary");
-  if (ix->records_only)
-    throw sme::Error(SME_EINVAL, "suggestions: records-only index (merged shard pieces): ask the shard indexes");
-  if (ix->K != 1) throw sme::Error(SME_EINVAL, "suggestions: K = " + std::to_string(ix->K) + " index (K = 1 only)");
+  need_vocabulary(ix, "suggestions", "ask the shard indexes");
 }
 
 int sme_index_suggest_terms_device(sme_index *ix, const uint8_t *words, const int64_t *offs, int n, int max_dist, int m,
@@ -807,10 +822,11 @@ int sme_index_suggest_terms_device(sme_index *ix, const uint8_t *words, const in
     need_suggest_args(ix, words, offs, n, max_dist, m);
     set_device(ix->ctx);
     sme::suggest_terms(ix, words, offs, n, max_dist, m, stream_of(ix->ctx, stream));
-    *d_sug_off = (const int64_t *)ix->d_fz_off.p;
-    *d_term_ids = (const int32_t *)ix->d_fz_ids.p;
-    *d_dist = (const uint8_t *)ix->d_fz_dist.p;
-    if (total) *total = ix->fz_total;
+    const sme::TermDists &r = ix->fz;
+    *d_sug_off = r.dev_offsets();
+    *d_term_ids = r.dev<sme::TermDists::ids>();
+    *d_dist = r.dev<sme::TermDists::dist>();
+    if (total) *total = r.total;
   });
 }
 
@@ -822,20 +838,11 @@ int sme_index_suggest_terms(sme_index *ix, const uint8_t *words, const int64_t *
     set_device(ix->ctx);
     hipStream_t st = ix->ctx->own_stream;
     sme::suggest_terms(ix, words, offs, n, max_dist, m, st);
-    const size_t tot = (size_t)ix->fz_total;
-    ix->h_fz_off.resize((size_t)n + 1);
-    ix->h_fz_ids.resize(tot + 1);  // (never an empty vector: data() stays a valid pointer)
-    ix->h_fz_dist.resize(tot + 1);
-    SME_HIP(hipMemcpyAsync(ix->h_fz_off.data(), ix->d_fz_off.p, ((size_t)n + 1) * sizeof(int64_t),
-                           hipMemcpyDeviceToHost, st));
-    if (tot) {
-      SME_HIP(hipMemcpyAsync(ix->h_fz_ids.data(), ix->d_fz_ids.p, tot * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-      SME_HIP(hipMemcpyAsync(ix->h_fz_dist.data(), ix->d_fz_dist.p, tot, hipMemcpyDeviceToHost, st));
-    }
-    SME_HIP(hipStreamSynchronize(st));
-    *sug_off = ix->h_fz_off.data();
-    *term_ids = ix->h_fz_ids.data();
-    *dist = ix->h_fz_dist.data();
+    sme::TermDists &r = ix->fz;
+    r.fetch(st);
+    *sug_off = r.h_off.data();
+    *term_ids = r.host<sme::TermDists::ids>();
+    *dist = r.host<sme::TermDists::dist>();
   });
 }
 
@@ -843,18 +850,41 @@ int sme_index_suggest_stats(const sme_index *ix, uint64_t *scanned_words, uint64
   return guard([&] {
     if (!ix || !scanned_words || !candidates) throw sme::Error(SME_EINVAL, "null argument");
     *scanned_words = ix->fz_scanned;
-    *candidates = ix->fz_cands;
+    *candidates = ix->fz.cands;
   });
 }
 
-// Boolean retrieval runs over the query side of a TermKGramDocIndexer index
+// Boolean retrieval and structured queries run over the query side of a
+// TermKGramDocIndexer index.  Which arrays a batch without entries may leave NULL
+// is each feature's own rule, checked after this.
+static void need_group_args(const sme_index *ix, const std::string &what, const int64_t *q_offsets, int nq, int order,
+                            int m) {
+  if (!ix || nq < 0 || (nq > 0 && !q_offsets)) throw sme::Error(SME_EINVAL, "bad argument");
+  if (ix->job != 0) throw sme::Error(SME_EINVAL, what + ": not a TermKGramDocIndexer index");
+  need_query_side(ix);
+  if (m < 0) throw sme::Error(SME_EINVAL, what + ": m must be >= 0");
+  if (order != 0 && order != 1) throw sme::Error(SME_EINVAL, what + ": order must be 0 (docno) or 1 (score)");
+}
+
+// the result of a Boolean or a structured call
+static void device_arrays(const sme::DocScores &r, const int64_t **d_res_off, const int32_t **d_docno,
+                          const double **d_score, int64_t *total) {
+  *d_res_off = r.dev_offsets();
+  *d_docno = r.dev<sme::DocScores::docno>();
+  *d_score = r.dev<sme::DocScores::score>();
+  if (total) *total = r.total;
+}
+static void host_arrays(sme::DocScores &r, hipStream_t st, const int64_t **res_off, const int32_t **docno,
+                        const double **score) {
+  r.fetch(st);
+  *res_off = r.h_off.data();
+  *docno = r.host<sme::DocScores::docno>();
+  *score = r.host<sme::DocScores::score>();
+}
+
 static void need_boolean_args(const sme_index *ix, const int32_t *term_ids, const int64_t *g_offsets,
                               const uint8_t *g_flags, const int64_t *q_offsets, int nq, int order, int m) {
-  if (!ix || nq < 0 || (nq > 0 && !q_offsets)) throw sme::Error(SME_EINVAL, "bad argument");
-  if (ix->job != 0) throw sme::Error(SME_EINVAL, "boolean: not a TermKGramDocIndexer index");
-  need_query_side(ix);
-  if (m < 0) throw sme::Error(SME_EINVAL, "boolean: m must be >= 0");
-  if (order != 0 && order != 1) throw sme::Error(SME_EINVAL, "boolean: order must be 0 (docno) or 1 (score)");
+  need_group_args(ix, "boolean", q_offsets, nq, order, m);
   // g_offsets always holds an entry; only a batch without a group may leave
   // g_flags and term_ids NULL (sme::query_boolean validates the offsets
   // themselves before anything is read through them)
@@ -871,10 +901,7 @@ int sme_query_boolean_device(sme_index *ix, const int32_t *term_ids, const int64
     need_boolean_args(ix, term_ids, g_offsets, g_flags, q_offsets, nq, order, m);
     set_device(ix->ctx);
     sme::query_boolean(ix, term_ids, g_offsets, g_flags, q_offsets, nq, order, m, stream_of(ix->ctx, stream));
-    *d_res_off = (const int64_t *)ix->d_bq_off.p;
-    *d_docno = (const int32_t *)ix->d_bq_docno.p;
-    *d_score = (const double *)ix->d_bq_score.p;
-    if (total) *total = ix->bq_total;
+    device_arrays(ix->bq, d_res_off, d_docno, d_score, total);
   });
 }
 
@@ -887,48 +914,55 @@ int sme_query_boolean(sme_index *ix, const int32_t *term_ids, const int64_t *g_o
     set_device(ix->ctx);
     hipStream_t st = ix->ctx->own_stream;
     sme::query_boolean(ix, term_ids, g_offsets, g_flags, q_offsets, nq, order, m, st);
-    const size_t tot = (size_t)ix->bq_total;
-    ix->h_bq_off.resize((size_t)nq + 1);
-    ix->h_bq_docno.resize(tot + 1);  // (never an empty vector: data() stays a valid pointer)
-    ix->h_bq_score.resize(tot + 1);
-    SME_HIP(hipMemcpyAsync(ix->h_bq_off.data(), ix->d_bq_off.p, ((size_t)nq + 1) * sizeof(int64_t),
-                           hipMemcpyDeviceToHost, st));
-    if (tot) {
-      SME_HIP(hipMemcpyAsync(ix->h_bq_docno.data(), ix->d_bq_docno.p, tot * sizeof(int32_t), hipMemcpyDeviceToHost,
-                             st));
-      SME_HIP(hipMemcpyAsync(ix->h_bq_score.data(), ix->d_bq_score.p, tot * sizeof(double), hipMemcpyDeviceToHost,
-                             st));
-    }
-    SME_HIP(hipStreamSynchronize(st));
-    *res_off = ix->h_bq_off.data();
-    *docno = ix->h_bq_docno.data();
-    *score = ix->h_bq_score.data();
+    host_arrays(ix->bq, st, res_off, docno, score);
   });
 }
 
 int sme_query_boolean_stats(const sme_index *ix, uint64_t *candidates, uint64_t *matches) {
   return guard([&] {
     if (!ix || !candidates || !matches) throw sme::Error(SME_EINVAL, "null argument");
-    *candidates = ix->bq_cands;
-    *matches = ix->bq_matches;
+    *candidates = ix->bq.cands;
+    *matches = ix->bq.matches;
   });
 }
 
-// Phrase queries run over the query side and the positions of a K = 1 index
-static void need_phrase_args(const sme_index *ix, const int32_t *term_ids, const int64_t *p_offsets, int np, int order,
-                             int m) {
-  if (!ix || np < 0 || (np > 0 && !p_offsets)) throw sme::Error(SME_EINVAL, "bad argument");
-  if (ix->job != 0) throw sme::Error(SME_EINVAL, "phrase query: not a TermKGramDocIndexer index");
-  if (ix->records_only)
-    throw sme::Error(SME_EINVAL, "phrase query: the index has no query side (merged shard pieces)");
-  if (ix->K != 1) throw sme::Error(SME_EINVAL, "phrase query: the index holds k-grams (K != 1), not terms");
+// Phrase and proximity queries run over the query side and the positions of a
+// K = 1 index.  term_ids may be NULL only in a batch without a term (the feature
+// validates the offsets themselves before anything is read through them).
+static void need_positions_args(const sme_index *ix, const std::string &what, const int32_t *term_ids,
+                                const int64_t *offsets, int n, int order, int m) {
+  if (!ix || n < 0 || (n > 0 && !offsets)) throw sme::Error(SME_EINVAL, "bad argument");
+  if (ix->job != 0) throw sme::Error(SME_EINVAL, what + ": not a TermKGramDocIndexer index");
+  if (ix->records_only) throw sme::Error(SME_EINVAL, what + ": the index has no query side (merged shard pieces)");
+  if (ix->K != 1) throw sme::Error(SME_EINVAL, what + ": the index holds k-grams (K != 1), not terms");
   if (!ix->has_positions)
-    throw sme::Error(SME_EINVAL, "phrase query: the index keeps no positions (build it with option \"positions\" 1)");
-  if (m < 0) throw sme::Error(SME_EINVAL, "phrase query: m must be >= 0");
-  if (order != 0 && order != 1) throw sme::Error(SME_EINVAL, "phrase query: order must be 0 (docno) or 1 (score)");
-  // term_ids may be NULL only in a batch without a term (sme::query_phrase
-  // validates the offsets themselves before anything is read through them)
-  if (np > 0 && p_offsets[np] != 0 && !term_ids) throw sme::Error(SME_EINVAL, "bad argument");
+    throw sme::Error(SME_EINVAL, what + ": the index keeps no positions (build it with option \"positions\" 1)");
+  if (m < 0) throw sme::Error(SME_EINVAL, what + ": m must be >= 0");
+  if (order != 0 && order != 1) throw sme::Error(SME_EINVAL, what + ": order must be 0 (docno) or 1 (score)");
+  if (n > 0 && offsets[n] != 0 && !term_ids) throw sme::Error(SME_EINVAL, "bad argument");
+}
+
+// the result of a phrase or a proximity call
+static void device_arrays(const sme::DocFreqScores &r, const int64_t **d_res_off, const int32_t **d_docno,
+                          const int32_t **d_freq, const double **d_score, int64_t *total) {
+  *d_res_off = r.dev_offsets();
+  *d_docno = r.dev<sme::DocFreqScores::docno>();
+  *d_freq = r.dev<sme::DocFreqScores::freq>();
+  *d_score = r.dev<sme::DocFreqScores::score>();
+  if (total) *total = r.total;
+}
+static void host_arrays(sme::DocFreqScores &r, hipStream_t st, const int64_t **res_off, const int32_t **docno,
+                        const int32_t **freq, const double **score) {
+  r.fetch(st);
+  *res_off = r.h_off.data();
+  *docno = r.host<sme::DocFreqScores::docno>();
+  *freq = r.host<sme::DocFreqScores::freq>();
+  *score = r.host<sme::DocFreqScores::score>();
+}
+static void pass_stats(const sme::DocFreqScores &r, uint64_t *candidates, uint64_t *verified, uint64_t *matches) {
+  *candidates = r.cands;
+  *verified = r.verified;
+  *matches = r.matches;
 }
 
 int sme_query_phrase_device(sme_index *ix, const int32_t *term_ids, const int64_t *p_offsets, int np, int order, int m,
@@ -936,14 +970,10 @@ int sme_query_phrase_device(sme_index *ix, const int32_t *term_ids, const int64_
                             const double **d_score, int64_t *total) {
   return guard([&] {
     if (!d_res_off || !d_docno || !d_freq || !d_score) throw sme::Error(SME_EINVAL, "null argument");
-    need_phrase_args(ix, term_ids, p_offsets, np, order, m);
+    need_positions_args(ix, "phrase query", term_ids, p_offsets, np, order, m);
     set_device(ix->ctx);
     sme::query_phrase(ix, term_ids, p_offsets, np, order, m, stream_of(ix->ctx, stream));
-    *d_res_off = (const int64_t *)ix->d_pq_off.p;
-    *d_docno = (const int32_t *)ix->d_pq_docno.p;
-    *d_freq = (const int32_t *)ix->d_pq_freq.p;
-    *d_score = (const double *)ix->d_pq_score.p;
-    if (total) *total = ix->pq_total;
+    device_arrays(ix->pq, d_res_off, d_docno, d_freq, d_score, total);
   });
 }
 
@@ -951,57 +981,26 @@ int sme_query_phrase(sme_index *ix, const int32_t *term_ids, const int64_t *p_of
                      const int64_t **res_off, const int32_t **docno, const int32_t **freq, const double **score) {
   return guard([&] {
     if (!res_off || !docno || !freq || !score) throw sme::Error(SME_EINVAL, "null argument");
-    need_phrase_args(ix, term_ids, p_offsets, np, order, m);
+    need_positions_args(ix, "phrase query", term_ids, p_offsets, np, order, m);
     set_device(ix->ctx);
     hipStream_t st = ix->ctx->own_stream;
     sme::query_phrase(ix, term_ids, p_offsets, np, order, m, st);
-    const size_t tot = (size_t)ix->pq_total;
-    ix->h_pq_off.resize((size_t)np + 1);
-    ix->h_pq_docno.resize(tot + 1);  // (never an empty vector: data() stays a valid pointer)
-    ix->h_pq_freq.resize(tot + 1);
-    ix->h_pq_score.resize(tot + 1);
-    SME_HIP(hipMemcpyAsync(ix->h_pq_off.data(), ix->d_pq_off.p, ((size_t)np + 1) * sizeof(int64_t),
-                           hipMemcpyDeviceToHost, st));
-    if (tot) {
-      SME_HIP(hipMemcpyAsync(ix->h_pq_docno.data(), ix->d_pq_docno.p, tot * sizeof(int32_t), hipMemcpyDeviceToHost,
-                             st));
-      SME_HIP(hipMemcpyAsync(ix->h_pq_freq.data(), ix->d_pq_freq.p, tot * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-      SME_HIP(hipMemcpyAsync(ix->h_pq_score.data(), ix->d_pq_score.p, tot * sizeof(double), hipMemcpyDeviceToHost,
-                             st));
-    }
-    SME_HIP(hipStreamSynchronize(st));
-    *res_off = ix->h_pq_off.data();
-    *docno = ix->h_pq_docno.data();
-    *freq = ix->h_pq_freq.data();
-    *score = ix->h_pq_score.data();
+    host_arrays(ix->pq, st, res_off, docno, freq, score);
   });
 }
 
 int sme_query_phrase_stats(const sme_index *ix, uint64_t *candidates, uint64_t *verified, uint64_t *matches) {
   return guard([&] {
     if (!ix || !candidates || !verified || !matches) throw sme::Error(SME_EINVAL, "null argument");
-    *candidates = ix->pq_cands;
-    *verified = ix->pq_verified;
-    *matches = ix->pq_matches;
+    pass_stats(ix->pq, candidates, verified, matches);
   });
 }
 
-// Proximity queries run over what phrase queries run over, and refuse what they refuse
+// (a proximity batch with queries also has a width and a kind for each)
 static void need_near_args(const sme_index *ix, const int32_t *term_ids, const int64_t *q_offsets,
                            const int32_t *widths, const uint8_t *kinds, int nq, int order, int m) {
-  if (!ix || nq < 0 || (nq > 0 && (!q_offsets || !widths || !kinds))) throw sme::Error(SME_EINVAL, "bad argument");
-  if (ix->job != 0) throw sme::Error(SME_EINVAL, "proximity query: not a TermKGramDocIndexer index");
-  if (ix->records_only)
-    throw sme::Error(SME_EINVAL, "proximity query: the index has no query side (merged shard pieces)");
-  if (ix->K != 1) throw sme::Error(SME_EINVAL, "proximity query: the index holds k-grams (K != 1), not terms");
-  if (!ix->has_positions)
-    throw sme::Error(SME_EINVAL,
-                     "proximity query: the index keeps no positions (build it with option \"positions\" 1)");
-  if (m < 0) throw sme::Error(SME_EINVAL, "proximity query: m must be >= 0");
-  if (order != 0 && order != 1) throw sme::Error(SME_EINVAL, "proximity query: order must be 0 (docno) or 1 (score)");
-  // term_ids may be NULL only in a batch without a term (sme::query_near validates
-  // the offsets themselves before anything is read through them)
-  if (nq > 0 && q_offsets[nq] != 0 && !term_ids) throw sme::Error(SME_EINVAL, "bad argument");
+  if (nq > 0 && (!widths || !kinds)) throw sme::Error(SME_EINVAL, "bad argument");
+  need_positions_args(ix, "proximity query", term_ids, q_offsets, nq, order, m);
 }
 
 int sme_query_near_device(sme_index *ix, const int32_t *term_ids, const int64_t *q_offsets, const int32_t *widths,
@@ -1012,11 +1011,7 @@ int sme_query_near_device(sme_index *ix, const int32_t *term_ids, const int64_t 
     need_near_args(ix, term_ids, q_offsets, widths, kinds, nq, order, m);
     set_device(ix->ctx);
     sme::query_near(ix, term_ids, q_offsets, widths, kinds, nq, order, m, stream_of(ix->ctx, stream));
-    *d_res_off = (const int64_t *)ix->d_nq_off.p;
-    *d_docno = (const int32_t *)ix->d_nq_docno.p;
-    *d_freq = (const int32_t *)ix->d_nq_freq.p;
-    *d_score = (const double *)ix->d_nq_score.p;
-    if (total) *total = ix->nq_total;
+    device_arrays(ix->nq, d_res_off, d_docno, d_freq, d_score, total);
   });
 }
 
@@ -1029,49 +1024,23 @@ int sme_query_near(sme_index *ix, const int32_t *term_ids, const int64_t *q_offs
     set_device(ix->ctx);
     hipStream_t st = ix->ctx->own_stream;
     sme::query_near(ix, term_ids, q_offsets, widths, kinds, nq, order, m, st);
-    const size_t tot = (size_t)ix->nq_total;
-    ix->h_nq_off.resize((size_t)nq + 1);
-    ix->h_nq_docno.resize(tot + 1);  // (never an empty vector: data() stays a valid pointer)
-    ix->h_nq_freq.resize(tot + 1);
-    ix->h_nq_score.resize(tot + 1);
-    SME_HIP(hipMemcpyAsync(ix->h_nq_off.data(), ix->d_nq_off.p, ((size_t)nq + 1) * sizeof(int64_t),
-                           hipMemcpyDeviceToHost, st));
-    if (tot) {
-      SME_HIP(hipMemcpyAsync(ix->h_nq_docno.data(), ix->d_nq_docno.p, tot * sizeof(int32_t), hipMemcpyDeviceToHost,
-                             st));
-      SME_HIP(hipMemcpyAsync(ix->h_nq_freq.data(), ix->d_nq_freq.p, tot * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-      SME_HIP(hipMemcpyAsync(ix->h_nq_score.data(), ix->d_nq_score.p, tot * sizeof(double), hipMemcpyDeviceToHost,
-                             st));
-    }
-    SME_HIP(hipStreamSynchronize(st));
-    *res_off = ix->h_nq_off.data();
-    *docno = ix->h_nq_docno.data();
-    *freq = ix->h_nq_freq.data();
-    *score = ix->h_nq_score.data();
+    host_arrays(ix->nq, st, res_off, docno, freq, score);
   });
 }
 
 int sme_query_near_stats(const sme_index *ix, uint64_t *candidates, uint64_t *verified, uint64_t *matches) {
   return guard([&] {
     if (!ix || !candidates || !verified || !matches) throw sme::Error(SME_EINVAL, "null argument");
-    *candidates = ix->nq_cands;
-    *verified = ix->nq_verified;
-    *matches = ix->nq_matches;
+    pass_stats(ix->nq, candidates, verified, matches);
   });
 }
 
-// Structured queries run over what Boolean retrieval runs over; a batch with an
-// operator leaf also needs what proximity queries need (sme::query_structured
-// says so once it has validated the batch and knows its leaves)
+// A structured batch with an operator leaf also needs what proximity queries need
+// (sme::query_structured says so once it has validated the batch and knows its leaves)
 static void need_structured_args(const sme_index *ix, const int32_t *term_ids, const int64_t *l_offsets,
                                  const uint8_t *l_kinds, const int32_t *l_widths, const int64_t *g_offsets,
                                  const uint8_t *g_flags, const int64_t *q_offsets, int nq, int order, int m) {
-  if (!ix || nq < 0 || (nq > 0 && !q_offsets)) throw sme::Error(SME_EINVAL, "bad argument");
-  if (ix->job != 0) throw sme::Error(SME_EINVAL, "structured query: not a TermKGramDocIndexer index");
-  need_query_side(ix);
-  if (m < 0) throw sme::Error(SME_EINVAL, "structured query: m must be >= 0");
-  if (order != 0 && order != 1)
-    throw sme::Error(SME_EINVAL, "structured query: order must be 0 (docno) or 1 (score)");
+  need_group_args(ix, "structured query", q_offsets, nq, order, m);
   // g_offsets and l_offsets always hold an entry; only a batch without a group may
   // leave the other arrays NULL (sme::query_structured validates the offsets
   // themselves before anything is read through them)
@@ -1091,10 +1060,7 @@ int sme_query_structured_device(sme_index *ix, const int32_t *term_ids, const in
     set_device(ix->ctx);
     sme::query_structured(ix, term_ids, l_offsets, l_kinds, l_widths, g_offsets, g_flags, q_offsets, nq, order, m,
                           stream_of(ix->ctx, stream));
-    *d_res_off = (const int64_t *)ix->d_sq_off.p;
-    *d_docno = (const int32_t *)ix->d_sq_docno.p;
-    *d_score = (const double *)ix->d_sq_score.p;
-    if (total) *total = ix->sq_total;
+    device_arrays(ix->sq, d_res_off, d_docno, d_score, total);
   });
 }
 
@@ -1108,22 +1074,7 @@ int sme_query_structured(sme_index *ix, const int32_t *term_ids, const int64_t *
     set_device(ix->ctx);
     hipStream_t st = ix->ctx->own_stream;
     sme::query_structured(ix, term_ids, l_offsets, l_kinds, l_widths, g_offsets, g_flags, q_offsets, nq, order, m, st);
-    const size_t tot = (size_t)ix->sq_total;
-    ix->h_sq_off.resize((size_t)nq + 1);
-    ix->h_sq_docno.resize(tot + 1);  // (never an empty vector: data() stays a valid pointer)
-    ix->h_sq_score.resize(tot + 1);
-    SME_HIP(hipMemcpyAsync(ix->h_sq_off.data(), ix->d_sq_off.p, ((size_t)nq + 1) * sizeof(int64_t),
-                           hipMemcpyDeviceToHost, st));
-    if (tot) {
-      SME_HIP(hipMemcpyAsync(ix->h_sq_docno.data(), ix->d_sq_docno.p, tot * sizeof(int32_t), hipMemcpyDeviceToHost,
-                             st));
-      SME_HIP(hipMemcpyAsync(ix->h_sq_score.data(), ix->d_sq_score.p, tot * sizeof(double), hipMemcpyDeviceToHost,
-                             st));
-    }
-    SME_HIP(hipStreamSynchronize(st));
-    *res_off = ix->h_sq_off.data();
-    *docno = ix->h_sq_docno.data();
-    *score = ix->h_sq_score.data();
+    host_arrays(ix->sq, st, res_off, docno, score);
   });
 }
 
@@ -1132,9 +1083,9 @@ int sme_query_structured_stats(const sme_index *ix, uint64_t *leaves, uint64_t *
   return guard([&] {
     if (!ix || !leaves || !verified || !candidates || !matches) throw sme::Error(SME_EINVAL, "null argument");
     *leaves = ix->sq_leaves;
-    *verified = ix->sq_verified;
-    *candidates = ix->sq_cands;
-    *matches = ix->sq_matches;
+    *verified = ix->sq.verified;
+    *candidates = ix->sq.cands;
+    *matches = ix->sq.matches;
   });
 }
 

@@ -211,10 +211,9 @@ void query_boolean(sme_index *ix, const int32_t *term_ids, const int64_t *g_offs
     default:
       throw Error(SME_EINVAL, "boolean " + where + "a term id outside [-1, V)");
   }
-  ix->bq_total = 0;
-  ix->bq_cands = 0;
-  ix->bq_matches = 0;
-  int64_t *d_roff = ix->d_bq_off.as<int64_t>((size_t)nq + 1);
+  DocScores &out = ix->bq;
+  out.reset();
+  int64_t *d_roff = out.offsets(nq);
   if (nq == 0) {
     SME_HIP(hipMemsetAsync(d_roff, 0, sizeof(int64_t), st));
     SME_HIP(hipStreamSynchronize(st));
@@ -255,11 +254,8 @@ void query_boolean(sme_index *ix, const int32_t *term_ids, const int64_t *g_offs
     const BoolOp op{b, sbeg, scnt, sq, qdrv, docno, w};
     const Counted c = count_chunks(op, (int)R, choff, scnt, chunk, mob, scn,
                                    "boolean: 2^31 or more matches in one batch", st, d_cands, &cands);
-    const int64_t out_total = bool_tail(cx, op, c, FirstRange{b.goff, b.qoff}, nq, order, m, d_roff, ix->d_bq_docno,
-                                        ix->d_bq_score, st);
-    ix->bq_total = out_total;
-    ix->bq_cands = (uint64_t)cands;
-    ix->bq_matches = (uint64_t)c.total;
+    bool_tail(cx, op, c, FirstRange{b.goff, b.qoff}, order, m, out, st);
+    out.cands = (uint64_t)cands;
   } catch (...) {
     (void)hipStreamSynchronize(st);  // the upload may still read `blob`, kernels the temporaries
     throw;

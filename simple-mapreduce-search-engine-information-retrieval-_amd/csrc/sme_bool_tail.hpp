@@ -54,13 +54,16 @@ __global__ void k_bool_gather(const uint32_t *__restrict__ qs, const uint32_t *_
   }
 }
 
-// The counted matches `c` of filter `op` -> d_roff[nq + 1] (result offsets after
-// the cut), out_docno / out_score sized for them; first(i) = query i's first range
-// (k_owner_offs).  Returns the results after the cut; synchronises the stream.
-// The temporaries are pooled blocks of the call.
+// The counted matches `c` of filter `op` -> `out`, whose offsets the caller has
+// sized for its out.n queries: the result offsets after the cut, docno and score
+// sized for them, total and matches (those before the cut); first(i) = query i's
+// first range (k_owner_offs).  Synchronises the stream.  The temporaries are
+// pooled blocks of the call.
 template <class Op, class First>
-int64_t bool_tail(sme_ctx *cx, const Op &op, const Counted &c, First first, int nq, int order, int m, int64_t *d_roff,
-                  DevBuf &out_docno_buf, DevBuf &out_score_buf, hipStream_t st) {
+void bool_tail(sme_ctx *cx, const Op &op, const Counted &c, First first, int order, int m, DocScores &out,
+               hipStream_t st) {
+  const int nq = out.n;
+  int64_t *d_roff = (int64_t *)out.off.p;
   DevBuf wob, kpb, scn, mdb, msb, mqb, ka, kb, pa, pb, pc, sa, sb, radix;
   for (DevBuf *b : {&wob, &kpb, &scn, &mdb, &msb, &mqb, &ka, &kb, &pa, &pb, &pc, &sa, &sb, &radix}) b->pool = &cx->pool;
   // (declared after the temporaries, so it runs before they go back to the pool:
@@ -84,8 +87,8 @@ int64_t bool_tail(sme_ctx *cx, const Op &op, const Counted &c, First first, int 
   int64_t out_total = 0;
   SME_HIP(hipMemcpyAsync(&out_total, d_roff + nq, sizeof(int64_t), hipMemcpyDeviceToHost, st));
   SME_HIP(hipStreamSynchronize(st));
-  int32_t *out_docno = out_docno_buf.as<int32_t>((size_t)out_total);
-  double *out_score = out_score_buf.as<double>((size_t)out_total);
+  int32_t *out_docno = out.alloc<DocScores::docno>(out_total);
+  double *out_score = out.alloc<DocScores::score>(out_total);
   if (total > 0) {
     const size_t T = (size_t)total;
     int32_t *mdoc = mdb.as<int32_t>(T);
@@ -116,7 +119,8 @@ int64_t bool_tail(sme_ctx *cx, const Op &op, const Counted &c, First first, int 
     SME_CHECK_LAUNCH();
   }
   SME_HIP(hipStreamSynchronize(st));
-  return out_total;
+  out.total = out_total;
+  out.matches = (uint64_t)total;
 }
 
 }  // namespace

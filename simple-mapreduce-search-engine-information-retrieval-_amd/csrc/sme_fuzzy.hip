@@ -211,9 +211,9 @@ __global__ void k_fuzzy_gather(const uint32_t *__restrict__ w, const uint32_t *_
 void suggest_terms(sme_index *ix, const uint8_t *words, const int64_t *offs, int n, int max_dist, int m,
                    hipStream_t st) {
   sme_ctx *cx = ix->ctx;
-  ix->fz_total = 0;
+  TermDists &out = ix->fz;
+  out.reset();
   ix->fz_scanned = 0;
-  ix->fz_cands = 0;
   const int NL = fuzzy::lists_for(max_dist);
   const bool scan = cx->opt_fuzzy_scan != 0;
   // parse on the host: units and distinct keys of the batch as CSR
@@ -242,7 +242,7 @@ void suggest_terms(sme_index *ix, const uint8_t *words, const int64_t *offs, int
       scanned += (scan || nk < NL) ? 1 : 0;
     }
   }
-  int64_t *d_soff = ix->d_fz_off.as<int64_t>((size_t)n + 1);
+  int64_t *d_soff = out.offsets(n);
   if (n == 0) {
     SME_HIP(hipMemsetAsync(d_soff, 0, sizeof(int64_t), st));
     SME_HIP(hipStreamSynchronize(st));
@@ -295,8 +295,8 @@ void suggest_terms(sme_index *ix, const uint8_t *words, const int64_t *offs, int
     int64_t out_total = 0;
     SME_HIP(hipMemcpyAsync(&out_total, d_soff + n, sizeof(int64_t), hipMemcpyDeviceToHost, st));
     SME_HIP(hipStreamSynchronize(st));
-    int32_t *ids = ix->d_fz_ids.as<int32_t>((size_t)out_total);
-    uint8_t *dist = ix->d_fz_dist.as<uint8_t>((size_t)out_total);
+    int32_t *ids = out.alloc<TermDists::ids>(out_total);
+    uint8_t *dist = out.alloc<TermDists::dist>(out_total);
     if (total > 0) {
       uint64_t *key0 = ka.as<uint64_t>((size_t)total), *key1 = kb.as<uint64_t>((size_t)total);
       uint32_t *w0 = wa.as<uint32_t>((size_t)total), *w1 = wb.as<uint32_t>((size_t)total);
@@ -313,9 +313,9 @@ void suggest_terms(sme_index *ix, const uint8_t *words, const int64_t *offs, int
       SME_CHECK_LAUNCH();
     }
     SME_HIP(hipStreamSynchronize(st));
-    ix->fz_total = out_total;
+    out.total = out_total;
+    out.cands = (uint64_t)cands;
     ix->fz_scanned = scanned;
-    ix->fz_cands = (uint64_t)cands;
   } catch (...) {
     (void)hipStreamSynchronize(st);  // the upload may still read `blob`, kernels the temporaries
     throw;

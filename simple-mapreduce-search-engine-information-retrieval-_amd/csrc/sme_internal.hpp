@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "sme_common.hpp"
+#include "sme_result.hpp"
 
 struct sme_ctx {
   sme::BufPool pool;  // declared first: destroyed after every DevBuf below
@@ -159,36 +160,17 @@ struct sme_index {
   int64_t wild_G = 0, wild_pairs = 0;
   bool wild_ready = false;
   float wild_ms = 0.0f;
-  // ... and the last expansion: its outputs (owned by the index until the next
-  // one), the uploaded batch, and scratch per pattern and per candidate chunk
-  sme::DevBuf d_wx_off;  // int64 [n + 1]   match offsets
-  sme::DevBuf d_wx_ids;  // int32 [total]   matching term ids
+  // ... and the last expansion (its result: sme_result.hpp), with the uploaded
+  // batch and scratch per pattern and per candidate chunk
+  sme::TermIds wx;
   sme::DevBuf d_wx_in, d_wx_plan, d_wx_choff, d_wx_moff, d_wx_scan;
-  int64_t wx_total = 0;
-  std::vector<int64_t> h_wx_off;
-  std::vector<int32_t> h_wx_ids;
-  // spelling suggestions (sme_fuzzy.hip): the last call's outputs (owned by the
-  // index until the next one; its temporaries are pooled blocks of the call) and
-  // what it counted
-  sme::DevBuf d_fz_off;   // int64 [n + 1]  suggestion offsets
-  sme::DevBuf d_fz_ids;   // int32 [total]  term ids
-  sme::DevBuf d_fz_dist;  // u8 [total]     their distances
-  int64_t fz_total = 0;
-  uint64_t fz_scanned = 0, fz_cands = 0;  // words that took the whole vocabulary; (word, term) pairs length-tested
-  std::vector<int64_t> h_fz_off;
-  std::vector<int32_t> h_fz_ids;
-  std::vector<uint8_t> h_fz_dist;
-  // Boolean retrieval (sme_bool.hip): the last call's outputs (owned by the index
-  // until the next one; its temporaries are pooled blocks of the call) and what
-  // it counted
-  sme::DevBuf d_bq_off;    // int64 [nq + 1]  result offsets
-  sme::DevBuf d_bq_docno;  // int32 [total]   matching documents
-  sme::DevBuf d_bq_score;  // double [total]  their scores
-  int64_t bq_total = 0;
-  uint64_t bq_cands = 0, bq_matches = 0;  // driver postings examined; matches before the cut
-  std::vector<int64_t> h_bq_off;
-  std::vector<int32_t> h_bq_docno;
-  std::vector<double> h_bq_score;
+  // spelling suggestions (sme_fuzzy.hip): the last call's result; cands counts the
+  // (word, term) pairs length-tested, fz_scanned the words that took the whole vocabulary
+  sme::TermDists fz;
+  uint64_t fz_scanned = 0;
+  // Boolean retrieval (sme_bool.hip): the last call's result; cands counts the
+  // driver postings examined
+  sme::DocScores bq;
   // positions (a K = 1 build with the "positions" option; sme_phrase.hip): the
   // records' term streams in docno-ascending record order -- a forward index.
   // Empty buffers (ps_records == 0 and nothing allocated) when the index keeps none.
@@ -198,50 +180,25 @@ struct sme_index {
   int64_t ps_records = 0, ps_terms = 0;
   bool has_positions = false;
   int64_t idf_N = 0;  // the N the weights were last computed with (build, sme_index_reweight)
-  // phrase queries: the last call's outputs (owned by the index until the next
-  // one; its temporaries are pooled blocks of the call) and what it counted
-  sme::DevBuf d_pq_off;    // int64 [np + 1]  result offsets
-  sme::DevBuf d_pq_docno;  // int32 [total]   matching documents
-  sme::DevBuf d_pq_freq;   // int32 [total]   occurrences of the phrase in each
-  sme::DevBuf d_pq_score;  // double [total]  their scores
-  int64_t pq_total = 0;
-  uint64_t pq_cands = 0, pq_verified = 0, pq_matches = 0;  // driver postings; filter survivors; matches before the cut
-  std::vector<int64_t> h_pq_off;
-  std::vector<int32_t> h_pq_docno, h_pq_freq;
-  std::vector<double> h_pq_score;
-  // proximity queries (sme_near.hip): the last call's outputs and counts, as for
-  // phrases, and the scorer table 1 + ln(f) for f < nq_lut_n -- d_lut's bits
-  // continued past max_tf (an unordered freq can pass it); filled on first use, it only grows
-  sme::DevBuf d_nq_off;    // int64 [nq + 1]  result offsets
-  sme::DevBuf d_nq_docno;  // int32 [total]   matching documents
-  sme::DevBuf d_nq_freq;   // int32 [total]   the query's count in each
-  sme::DevBuf d_nq_score;  // double [total]  their scores
-  sme::DevBuf d_nq_lut;    // double [nq_lut_n]
+  // phrase queries: the last call's result (freq: occurrences of the phrase);
+  // cands counts the driver postings, verified the filter's survivors
+  sme::DocFreqScores pq;
+  // proximity queries (sme_near.hip): the last call's result, as for phrases, and
+  // the scorer table 1 + ln(f) for f < nq_lut_n -- d_lut's bits continued past
+  // max_tf (an unordered freq can pass it); filled on first use, it only grows
+  sme::DocFreqScores nq;
+  sme::DevBuf d_nq_lut;  // double [nq_lut_n]
   int64_t nq_lut_n = 0;
   int64_t nq_max_span = -1;  // the most stream positions of one docno (-1: not yet found), a bound on any freq
-  int64_t nq_total = 0;
-  uint64_t nq_cands = 0, nq_verified = 0, nq_matches = 0;  // driver postings; filter survivors; matches before the cut
-  std::vector<int64_t> h_nq_off;
-  std::vector<int32_t> h_nq_docno, h_nq_freq;
-  std::vector<double> h_nq_score;
-  // structured queries (sme_structq.hip): the last call's outputs and counts, and
-  // the virtual posting lists of its operator leaves -- leaf i's documents (docno
-  // ascending) and values at [d_sv_off[i], d_sv_off[i + 1]), written by the
-  // proximity pass (sv_*: that pass's counts)
-  sme::DevBuf d_sq_off;    // int64 [nq + 1]  result offsets
-  sme::DevBuf d_sq_docno;  // int32 [total]   matching documents
-  sme::DevBuf d_sq_score;  // double [total]  their scores
-  sme::DevBuf d_sv_off;    // int64 [leaves + 1]
-  sme::DevBuf d_sv_docno;  // int32 [sv_total]
-  sme::DevBuf d_sv_freq;   // int32 [sv_total]
-  sme::DevBuf d_sv_score;  // double [sv_total]
-  int64_t sq_total = 0, sv_total = 0;
-  uint64_t sv_cands = 0, sv_verified = 0, sv_matches = 0;
-  // operator leaves evaluated; (leaf, document) pairs scanned; driver entries examined; matches before the cut
-  uint64_t sq_leaves = 0, sq_verified = 0, sq_cands = 0, sq_matches = 0;
-  std::vector<int64_t> h_sq_off;
-  std::vector<int32_t> h_sq_docno;
-  std::vector<double> h_sq_score;
+  // structured queries (sme_structq.hip): the last call's result (verified: (leaf,
+  // document) pairs scanned; cands: driver entries examined) and the operator
+  // leaves evaluated, and in sv the virtual posting lists of those leaves -- leaf
+  // i's documents (docno ascending) and values at its offsets i, i + 1 -- written by
+  // the proximity pass with that pass's counts.  sv is no alias of nq: a structured
+  // call leaves a proximity result alone.
+  sme::DocScores sq;
+  uint64_t sq_leaves = 0;
+  sme::DocFreqScores sv;
   // stage timings of the build that produced this index (ms)
   std::vector<std::pair<std::string, float>> profile;
   ~sme_index() { ctx->live_indexes--; }  // members (pooled buffers) are released after this body
@@ -249,11 +206,11 @@ struct sme_index {
     c->live_indexes++;
     for (sme::DevBuf *b : {&d_term_off, &d_term_chars, &d_off, &d_docno_d, &d_tf_d, &d_w, &d_idf, &d_lut, &d_gram, &d_docno_o,
                            &d_tf_o, &d_rec_docno, &d_rec_first, &d_ser, &d_hrow_of, &d_heavy, &d_spk, &d_wkeys, &d_wgoff,
-                           &d_wgterm, &d_wx_off, &d_wx_ids, &d_wx_in, &d_wx_plan, &d_wx_choff, &d_wx_moff, &d_wx_scan, &d_fz_off,
-                           &d_fz_ids, &d_fz_dist, &d_bq_off, &d_bq_docno, &d_bq_score, &d_ps_off, &d_ps_terms, &d_ps_docno,
-                           &d_pq_off, &d_pq_docno, &d_pq_freq, &d_pq_score, &d_nq_off, &d_nq_docno, &d_nq_freq, &d_nq_score,
-                           &d_nq_lut, &d_sq_off, &d_sq_docno, &d_sq_score, &d_sv_off, &d_sv_docno, &d_sv_freq, &d_sv_score})
+                           &d_wgterm, &d_wx_in, &d_wx_plan, &d_wx_choff, &d_wx_moff, &d_wx_scan, &d_ps_off, &d_ps_terms,
+                           &d_ps_docno, &d_nq_lut})
       b->pool = &c->pool;
+    for (sme::ResultSet *r : std::initializer_list<sme::ResultSet *>{&wx, &fz, &bq, &pq, &nq, &sq, &sv})
+      r->bind(&c->pool);
   }
 };
 
@@ -410,41 +367,29 @@ int64_t count_shared_keys(sme_ctx *cx, const uint64_t *rows, int64_t n, hipStrea
 void lookup_terms(sme_index *ix, const std::vector<std::vector<uint16_t>> &terms, int32_t *ids,
                   hipStream_t st);
 // wildcard expansion (sme_wild.hip): the vocabulary's trigram table (built once),
-// and a batch of n UTF-8 patterns -> ix->d_wx_off / d_wx_ids / wx_total
+// and a batch of n UTF-8 patterns -> ix->wx
 void prepare_wildcards(sme_index *ix, hipStream_t st);
 void expand_wildcards(sme_index *ix, const uint8_t *patterns, const int64_t *offs, int n, hipStream_t st);
 // spelling suggestions (sme_fuzzy.hip): a batch of n UTF-8 words -> per word the
-// terms within max_dist edits, ordered and cut to m: ix->d_fz_off / d_fz_ids /
-// d_fz_dist / fz_total, and the call's counts fz_scanned / fz_cands
+// terms within max_dist edits, ordered and cut to m: ix->fz, and ix->fz_scanned
 void suggest_terms(sme_index *ix, const uint8_t *words, const int64_t *offs, int n, int max_dist, int m,
                    hipStream_t st);
 // Boolean retrieval (sme_bool.hip): nq queries of required / excluded term groups
 // (host arrays, validated here) -> per query the matching documents and scores,
-// ordered (0 docno asc, 1 score desc then docno asc) and cut to m: ix->d_bq_off /
-// d_bq_docno / d_bq_score / bq_total, and the call's counts bq_cands / bq_matches
+// ordered (0 docno asc, 1 score desc then docno asc) and cut to m: ix->bq
 void query_boolean(sme_index *ix, const int32_t *term_ids, const int64_t *g_offsets, const uint8_t *g_flags,
                    const int64_t *q_offsets, int nq, int order, int m, hipStream_t st);
 // phrase queries (sme_phrase.hip): np phrases of term ids (host arrays, validated
 // here) over the positions a K = 1 build kept -> per phrase the matching documents
 // with the phrase's frequency and score, ordered (0 docno asc, 1 score desc then
-// docno asc) and cut to m: ix->d_pq_off / d_pq_docno / d_pq_freq / d_pq_score /
-// pq_total, and the call's counts pq_cands / pq_verified / pq_matches
+// docno asc) and cut to m: ix->pq
 void query_phrase(sme_index *ix, const int32_t *term_ids, const int64_t *p_offsets, int np, int order, int m,
                   hipStream_t st);
 // proximity queries (sme_near.hip): nq queries of term ids with a width and a kind
 // each (0 ordered window, 1 unordered; host arrays, validated here) over the same
-// positions, through the same pass -> ix->d_nq_off / d_nq_docno / d_nq_freq /
-// d_nq_score / nq_total, and the call's counts nq_cands / nq_verified / nq_matches
+// positions, through the same pass -> ix->nq
 void query_near(sme_index *ix, const int32_t *term_ids, const int64_t *q_offsets, const int32_t *widths,
                 const uint8_t *kinds, int nq, int order, int m, hipStream_t st);
-// Where a phrase / proximity pass (sme_phrase_pass.hpp) leaves its results on the
-// index: the output buffers (owned by the index until the feature's next call) and
-// the call's counts.
-struct PassOut {
-  DevBuf &off, &docno, &freq, &score;
-  int64_t &total;
-  uint64_t &cands, &verified, &matches;
-};
 // What narrows a proximity pass (structured queries): pass query i cannot be a
 // result outside any of the groups [qgoff[owner[i]], qgoff[owner[i] + 1]), group g
 // being the union of the posting lists of terms[goff[g] .. goff[g + 1]) (-1: an
@@ -459,14 +404,13 @@ struct NarrowSpec {
 };
 // query_near behind its validation: the batch through the pass into `out`, the
 // candidate filter narrowed by `narrow` if given (sme_near.hip)
-void near_pass(sme_index *ix, const PassOut &out, const int32_t *term_ids, const int64_t *q_offsets,
+void near_pass(sme_index *ix, DocFreqScores &out, const int32_t *term_ids, const int64_t *q_offsets,
                const int32_t *widths, const uint8_t *kinds, int nq, int order, int m, const NarrowSpec *narrow,
                hipStream_t st);
 // structured queries (sme_structq.hip): nq queries of required / excluded groups of
 // leaves -- a term, or an ordered / unordered window over terms (host arrays,
 // validated here) -> per query the matching documents and scores, ordered and cut
-// as query_boolean's: ix->d_sq_off / d_sq_docno / d_sq_score / sq_total, and the
-// call's counts sq_leaves / sq_verified / sq_cands / sq_matches
+// as query_boolean's: ix->sq, and ix->sq_leaves
 void query_structured(sme_index *ix, const int32_t *term_ids, const int64_t *l_offsets, const uint8_t *l_kinds,
                       const int32_t *l_widths, const int64_t *g_offsets, const uint8_t *g_flags,
                       const int64_t *q_offsets, int nq, int order, int m, hipStream_t st);

@@ -169,12 +169,10 @@ void query_near(sme_index *ix, const int32_t *term_ids, const int64_t *q_offsets
     const bool limit = near::describe(rc, bad, msg, sizeof msg);
     throw Error(limit ? SME_ELIMIT : SME_EINVAL, msg);
   }
-  const PassOut out{ix->d_nq_off, ix->d_nq_docno, ix->d_nq_freq,    ix->d_nq_score,
-                    ix->nq_total, ix->nq_cands,   ix->nq_verified, ix->nq_matches};
-  near_pass(ix, out, term_ids, q_offsets, widths, kinds, nq, order, m, nullptr, st);
+  near_pass(ix, ix->nq, term_ids, q_offsets, widths, kinds, nq, order, m, nullptr, st);
 }
 
-void near_pass(sme_index *ix, const PassOut &out, const int32_t *term_ids, const int64_t *q_offsets,
+void near_pass(sme_index *ix, DocFreqScores &out, const int32_t *term_ids, const int64_t *q_offsets,
                const int32_t *widths, const uint8_t *kinds, int nq, int order, int m, const NarrowSpec *narrow,
                hipStream_t st) {
   Blob blob;  // one upload: term offsets | term ids | widths | kinds (| the narrowing tables)
@@ -267,8 +265,7 @@ void near_pass(sme_index *ix, const PassOut &out, const int32_t *term_ids, const
     SME_HIP(hipMemcpyAsync(&over, d_over, sizeof over, hipMemcpyDeviceToHost, st));
     SME_HIP(hipStreamSynchronize(st));
     if (over) {
-      out.total = 0;  // the call returns nothing, and its stats say so
-      out.cands = out.verified = out.matches = 0;
+      out.reset();  // the call returns nothing, and its stats say so
       SME_HIP(hipMemsetAsync(out.off.p, 0, ((size_t)nq + 1) * sizeof(int64_t), st));
       SME_HIP(hipStreamSynchronize(st));
       throw Error(SME_ELIMIT, "proximity query: " + std::to_string(over) +

@@ -79,11 +79,9 @@ void query_phrase(sme_index *ix, const int32_t *term_ids, const int64_t *p_offse
     a_poff = blob.add(p_offsets, (size_t)np + 1);
     a_term = blob.add(term_ids, (size_t)p_offsets[np]);
   }
-  const PassOut out{ix->d_pq_off, ix->d_pq_docno, ix->d_pq_freq,    ix->d_pq_score,
-                    ix->pq_total, ix->pq_cands,   ix->pq_verified, ix->pq_matches};
   run_pass(
-      ix, out, blob, a_poff, a_term, np, order, m, "phrase query: 2^31 or more candidate documents in one batch", st,
-      PlainFilter{},
+      ix, ix->pq, blob, a_poff, a_term, np, order, m, "phrase query: 2^31 or more candidate documents in one batch",
+      st, PlainFilter{},
       [&](const uint8_t *, Batch b, const int32_t *cdoc, const uint32_t *cph, int64_t C, int32_t *freq, uint8_t *flag) {
         hipLaunchKernelGGL(k_phrase_verify, dim3(verify_grid(C)), dim3(kVerifyNT), 0, st, b, cdoc, cph, C,
                            (const int64_t *)ix->d_ps_off.p, (const int32_t *)ix->d_ps_terms.p,

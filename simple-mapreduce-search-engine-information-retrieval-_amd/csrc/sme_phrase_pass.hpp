@@ -294,8 +294,8 @@ struct PlainFilter {  // run_pass's make_op of a pass that filters by the phrase
   PhraseOp operator()(const uint8_t *, const PhraseOp &p) const { return p; }
 };
 
-// One pass over a validated batch of np queries into `out` (PassOut,
-// sme_internal.hpp): `blob` is the upload, holding the term offsets at a_poff and
+// One pass over a validated batch of np queries into `out`, the feature's result
+// on the index: `blob` is the upload, holding the term offsets at a_poff and
 // the term ids at a_term beside whatever else the feature's kernels read.
 //   make_op(d_in, phrase_op)  the chunk filter's Op: PhraseOp itself (PlainFilter),
 //       or one that tests more on top of it (d_in: the uploaded blob)
@@ -305,14 +305,11 @@ struct PlainFilter {  // run_pass's make_op of a pass that filters by the phrase
 //       the score kernel over the T matches
 // `limit` is the SME_ELIMIT message at 2^31 candidates or more.
 template <class MakeOp, class Verify, class Score>
-void run_pass(sme_index *ix, const PassOut &out, const Blob &blob, size_t a_poff, size_t a_term, int np, int order,
+void run_pass(sme_index *ix, DocFreqScores &out, const Blob &blob, size_t a_poff, size_t a_term, int np, int order,
               int m, const char *limit, hipStream_t st, MakeOp make_op, Verify verify, Score score) {
   sme_ctx *cx = ix->ctx;
-  out.total = 0;
-  out.cands = 0;
-  out.verified = 0;
-  out.matches = 0;
-  int64_t *d_roff = out.off.as<int64_t>((size_t)np + 1);
+  out.reset();
+  int64_t *d_roff = out.offsets(np);
   SME_HIP(hipMemsetAsync(d_roff, 0, ((size_t)np + 1) * sizeof(int64_t), st));
   if (np == 0) {
     SME_HIP(hipStreamSynchronize(st));
@@ -388,9 +385,9 @@ void run_pass(sme_index *ix, const PassOut &out, const Blob &blob, size_t a_poff
         SME_HIP(hipMemcpyAsync((void *)d_tab, tab_h.bytes.data(), tab_h.bytes.size(), hipMemcpyHostToDevice, st));
         SME_HIP(hipMemcpyAsync(d_roff, d_tab + a_roff, ((size_t)np + 1) * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
         const double *d_idf = (const double *)(d_tab + a_idf);
-        int32_t *out_docno = out.docno.as<int32_t>((size_t)out_total);
-        int32_t *out_freq = out.freq.as<int32_t>((size_t)out_total);
-        double *out_score = out.score.as<double>((size_t)out_total);
+        int32_t *out_docno = out.alloc<DocFreqScores::docno>(out_total);
+        int32_t *out_freq = out.alloc<DocFreqScores::freq>(out_total);
+        double *out_score = out.alloc<DocFreqScores::score>(out_total);
         int32_t *mdoc = mdb.as<int32_t>((size_t)T);
         uint32_t *mph = mpb.as<uint32_t>((size_t)T);
         int32_t *mfreq = mfb.as<int32_t>((size_t)T);

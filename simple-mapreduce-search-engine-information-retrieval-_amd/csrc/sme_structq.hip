@@ -226,9 +226,10 @@ void query_structured(sme_index *ix, const int32_t *term_ids, const int64_t *l_o
     if (!ix->has_positions)
       throw Error(SME_EINVAL, "proximity query: the index keeps no positions (build it with option \"positions\" 1)");
   }
-  ix->sq_total = 0;
-  ix->sq_leaves = ix->sq_verified = ix->sq_cands = ix->sq_matches = 0;
-  int64_t *d_roff = ix->d_sq_off.as<int64_t>((size_t)nq + 1);
+  DocScores &out = ix->sq;
+  out.reset();
+  ix->sq_leaves = 0;
+  int64_t *d_roff = out.offsets(nq);
   if (nq == 0) {
     SME_HIP(hipMemsetAsync(d_roff, 0, sizeof(int64_t), st));
     SME_HIP(hipStreamSynchronize(st));
@@ -281,11 +282,9 @@ void query_structured(sme_index *ix, const int32_t *term_ids, const int64_t *l_o
       }
       spec.qgoff.push_back((int64_t)spec.goff.size() - 1);
     }
-    const PassOut out{ix->d_sv_off, ix->d_sv_docno, ix->d_sv_freq,    ix->d_sv_score,
-                      ix->sv_total, ix->sv_cands,   ix->sv_verified, ix->sv_matches};
-    near_pass(ix, out, n_terms.data(), n_off.data(), n_widths.data(), n_kinds.data(), (int)ops, 0, 0,
+    near_pass(ix, ix->sv, n_terms.data(), n_off.data(), n_widths.data(), n_kinds.data(), (int)ops, 0, 0,
               narrowing ? &spec : nullptr, st);
-    verified = ix->sv_verified;
+    verified = ix->sv.verified;
   }
   // one upload: leaf offsets | group offsets | leaf table | flags
   Blob blob;
@@ -311,7 +310,7 @@ void query_structured(sme_index *ix, const int32_t *term_ids, const int64_t *l_o
     int64_t *choff = chb.as<int64_t>((size_t)R + 1);
     unsigned long long *d_cands = cnd.as<unsigned long long>(1);
     const int64_t *doff = (const int64_t *)ix->d_off.p;
-    const int64_t *voff = ops > 0 ? (const int64_t *)ix->d_sv_off.p : nullptr;
+    const int64_t *voff = ops > 0 ? ix->sv.dev_offsets() : nullptr;
     SME_HIP(hipMemsetAsync(d_cands, 0, sizeof(unsigned long long), st));
     hipLaunchKernelGGL(k_structq_plan, dim3(grid_for((int64_t)nq + 1)), dim3(kNT), 0, st, b, nq, nl, doff, voff, chunk,
                        (int)cx->opt_bool_driver, sbeg, scnt, svirt, sq, qdrv, choff, d_cands);
@@ -325,17 +324,14 @@ void query_structured(sme_index *ix, const int32_t *term_ids, const int64_t *l_o
                       qdrv,
                       (const int32_t *)ix->d_docno_d.p,
                       (const double *)ix->d_w.p,
-                      ops > 0 ? (const int32_t *)ix->d_sv_docno.p : nullptr,
-                      ops > 0 ? (const double *)ix->d_sv_score.p : nullptr};
+                      ops > 0 ? ix->sv.dev<DocFreqScores::docno>() : nullptr,
+                      ops > 0 ? ix->sv.dev<DocFreqScores::score>() : nullptr};
     const Counted c = count_chunks(op, (int)R, choff, scnt, chunk, mob, scn,
                                    "structured query: 2^31 or more matches in one batch", st, d_cands, &cands);
-    const int64_t out_total = bool_tail(cx, op, c, FirstRange{b.goff, b.qoff}, nq, order, m, d_roff, ix->d_sq_docno,
-                                        ix->d_sq_score, st);
-    ix->sq_total = out_total;
+    bool_tail(cx, op, c, FirstRange{b.goff, b.qoff}, order, m, out, st);
     ix->sq_leaves = (uint64_t)ops;
-    ix->sq_verified = verified;
-    ix->sq_cands = (uint64_t)cands;
-    ix->sq_matches = (uint64_t)c.total;
+    out.verified = verified;
+    out.cands = (uint64_t)cands;
   } catch (...) {
     (void)hipStreamSynchronize(st);  // the upload may still read `blob`, kernels the temporaries
     throw;

@@ -235,7 +235,8 @@ void prepare_wildcards(sme_index *ix, hipStream_t st) {
 
 void expand_wildcards(sme_index *ix, const uint8_t *patterns, const int64_t *offs, int n, hipStream_t st) {
   sme_ctx *cx = ix->ctx;
-  ix->wx_total = 0;
+  TermIds &out = ix->wx;
+  out.reset();
   // parse on the host: units, masks and gram keys of the batch as CSR
   std::vector<int32_t> uoff(n + 1, 0), goff(n + 1, 0);
   std::vector<uint16_t> units;
@@ -262,7 +263,7 @@ void expand_wildcards(sme_index *ix, const uint8_t *patterns, const int64_t *off
       goff[i + 1] = (int32_t)gkeys.size();
     }
   }
-  int64_t *d_moffs = ix->d_wx_off.as<int64_t>((size_t)n + 1);
+  int64_t *d_moffs = out.offsets(n);
   if (n == 0) {
     SME_HIP(hipMemsetAsync(d_moffs, 0, sizeof(int64_t), st));
     SME_HIP(hipStreamSynchronize(st));
@@ -295,12 +296,12 @@ void expand_wildcards(sme_index *ix, const uint8_t *patterns, const int64_t *off
                     (const uint16_t *)ix->d_term_chars.p};
     const Counted c = count_chunks(op, n, choff, ccnt, chunk, ix->d_wx_moff, ix->d_wx_scan,
                                    "wildcard expansion: 2^31 or more matches in one batch", st);
-    emit_chunks(op, c, st, ix->d_wx_ids.as<int32_t>((size_t)c.total));
+    emit_chunks(op, c, st, out.alloc<TermIds::ids>(c.total));
     hipLaunchKernelGGL(k_owner_offs<FirstRange>, dim3(grid_for(n + 1)), dim3(kNT), 0, st, FirstRange{}, c.choff,
                        c.moff, (int64_t)n, d_moffs);
     SME_CHECK_LAUNCH();
     SME_HIP(hipStreamSynchronize(st));
-    ix->wx_total = c.total;
+    out.total = c.total;
   } catch (...) {
     (void)hipStreamSynchronize(st);  // the upload may still read `blob`
     throw;

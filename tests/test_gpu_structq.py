@@ -341,6 +341,95 @@ def test_device_entry_and_independent_buffers(sme):
     assert ix.query_structured_device(none)[3] == 0
 
 
+def test_host_arrays_live_until_the_features_next_call(sme):
+    """include/sme.h's promise for the host entries, seen through the C ABI itself (the
+    Python wrappers copy at once): the arrays one feature's host entry hands out stay
+    as they are while the other five features' host entries and all six device
+    entries run; a batch without a result still hands out valid column pointers; and
+    the feature answers its first batch again after that."""
+    corpus, mapping, _ = _craft()
+    ix = _ctx(sme, mapping, 1, 0).build(corpus)
+    L = sme.lib()
+    kilo, lima, mike, zulu = _words(ix, "kilo", "lima", "mike", "zulu")
+    i32, i64, u8, f64 = C.c_int32, C.c_int64, C.c_uint8, C.c_double
+    CT = {np.int32: i32, np.int64: i64, np.uint8: u8}
+
+    def typed(arrays, dtypes):  # (one element behind an empty array, as the wrappers keep)
+        keep = [np.ascontiguousarray(a, dt) if len(a) else np.zeros(1, dt) for a, dt in zip(arrays, dtypes)]
+        return keep, [a.ctypes.data_as(C.POINTER(CT[dt])) for a, dt in zip(keep, dtypes)]
+
+    def text(words, *more):
+        bs = [w.encode() for w in words]
+        offs = np.cumsum([0] + [len(b) for b in bs]).astype(np.int64)
+        return offs, [b"".join(bs), offs.ctypes.data_as(C.POINTER(i64)), len(bs), *more], len(bs)
+
+    def ids(arrays, dtypes, nq_at, order, m):
+        keep, ptrs = typed(arrays, dtypes)
+        nq = len(arrays[nq_at]) - 1
+        return keep, ptrs + [nq, order, m], nq
+
+    I = sme.Index
+    phrase = ([kilo, lima], 1, 1)
+    # feature: (host entry, device entry, column ctypes, arguments of a batch, first / other / empty batch)
+    features = {
+        "wx": (L.sme_index_expand_wildcards, L.sme_index_expand_wildcards_device, (i32,), lambda b: text(b),
+               ["k*", "zul*"], ["m*", "*a"], ["xyzzy*", "q?q"]),
+        "fz": (L.sme_index_suggest_terms, L.sme_index_suggest_terms_device, (i32, u8), lambda b: text(b, 1, 10),
+               ["kilo", "limo", "zulo"], ["mikes"], ["qqqqqqqqqq", "xxxxxxxx"]),
+        "bq": (L.sme_query_boolean, L.sme_query_boolean_device, (i32, f64),
+               lambda b: ids(I.boolean_arrays(b), (np.int32, np.int64, np.uint8, np.int64), 3, 1, 5),
+               [[([kilo], False), ([mike], False)], [([zulu], False)]], [[([lima], False)]], [[([-1], False)], []]),
+        "pq": (L.sme_query_phrase, L.sme_query_phrase_device, (i32, i32, f64),
+               lambda b: ids(I.phrase_arrays(b), (np.int32, np.int64), 1, 0, 6),
+               [[kilo, lima], [lima, zulu]], [[zulu, mike]], [[-1, kilo], [lima, kilo]]),
+        "nq": (L.sme_query_near, L.sme_query_near_device, (i32, i32, f64),
+               lambda b: ids(I.near_arrays(b), (np.int32, np.int64, np.int32, np.uint8), 1, 1, 7),
+               [([lima, kilo], 4, False), ([kilo, lima], 1, True)], [([kilo], 1, True)], [([-1, kilo], 2, True)]),
+        "sq": (L.sme_query_structured, L.sme_query_structured_device, (i32, f64),
+               lambda b: ids(I.structured_arrays(b),
+                             (np.int32, np.int64, np.uint8, np.int32, np.int64, np.uint8, np.int64), 6, 1, 9),
+               [[([phrase], REQ), ([T(mike)], REQ)], [([T(zulu), ([mike, kilo], 2, 9)], REQ)]],
+               [[([T(lima)], REQ)]], [[([T(-1)], REQ)], [([phrase], REQ), ([T(-1)], REQ)]]),
+    }
+
+    def host(name, batch):
+        """-> (queries, the raw pointers handed out: offsets, then every column)"""
+        entry, _, cols, args, *_ = features[name]
+        keep, a, n = args(batch)
+        outs = [C.POINTER(ct)() for ct in (i64,) + cols]
+        assert entry(ix._h, *a, *[C.byref(o) for o in outs]) == 0, L.sme_last_error()
+        return n, outs
+
+    def device(name, batch):
+        _, entry, cols, args, *_ = features[name]
+        keep, a, n = args(batch)
+        outs, tot = [C.c_void_p() for _ in range(len(cols) + 1)], i64()
+        assert entry(ix._h, *a, None, *[C.byref(o) for o in outs], C.byref(tot)) == 0, L.sme_last_error()
+
+    def read(n, outs):
+        """what the pointers point at now, as bytes: offsets[n + 1], then every column[total]"""
+        off = np.ctypeslib.as_array(outs[0], (n + 1,))
+        total = int(off[n])
+        return [off.tobytes()] + [np.ctypeslib.as_array(o, (total,)).tobytes() if total else b"" for o in outs[1:]]
+
+    for name, (_, _, cols, _, first, other, empty) in features.items():
+        n, outs = host(name, first)
+        copy = read(n, outs)
+        assert all(len(c) > 0 for c in copy[1:]) and len(copy) == len(cols) + 1, name  # the batch has results
+        for o in features:
+            if o != name:
+                host(o, features[o][5])
+        for o in features:
+            device(o, features[o][5])
+        assert read(n, outs) == copy, name
+        # a batch with queries and no result: valid pointers, every offset 0
+        ne, eouts = host(name, empty)
+        assert all(bool(p) for p in eouts), name
+        assert np.ctypeslib.as_array(eouts[0], (ne + 1,)).tolist() == [0] * (ne + 1), name
+        # ... after which the arrays serve the first batch again
+        assert read(*host(name, first)) == copy, name
+
+
 # ---- 6. refusals ---------------------------------------------------------------------
 def test_refusals(sme):
     corpus, mapping, _ = _craft()
