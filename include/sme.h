@@ -153,6 +153,10 @@ void sme_destroy(sme_ctx *ctx);
  *   "struct_narrow" structured queries (sme_query_structured): 1 (default) a query's required
  *                   term-only groups cut its operator leaves' candidates before their records
  *                   are scanned, 0 every leaf is evaluated whole.  Results are the same
+ *   "fb_slots"      relevance feedback (sme_index_feedback_terms): entries of the on-chip term
+ *                   table of one document set, a power of two in 16..4096 (default 4096, 48 KiB
+ *                   of LDS: two workgroups fit a CU); a set with more than 3/4 of that many
+ *                   distinct terms takes the large path.  Results are the same
  * Unknown names and out-of-range values are SME_EINVAL. */
 int sme_set_option(sme_ctx *ctx, const char *name, int64_t value);
 
@@ -634,6 +638,73 @@ int sme_query_structured_device(sme_index *ix, const int32_t *term_ids, const in
                                 const double **d_score, int64_t *total);
 int sme_query_structured_stats(const sme_index *ix, uint64_t *leaves, uint64_t *verified, uint64_t *candidates,
                                uint64_t *matches);
+
+/* Relevance feedback: from documents to terms (no reference counterpart).  Given
+ * sets of documents, the terms that characterise each set -- the expansion terms
+ * of pseudo-relevance feedback (Rocchio), or the query of "more like this" -- from
+ * the term streams a K = 1 index keeps (sme_index_positions).  sme_query_topk does
+ * the rest.
+ * Set i is the docnos docnos[f_offsets[i] .. f_offsets[i + 1]) (nq + 1 entries from
+ * 0).  An entry equal to -1 is skipped (sme_query_topk's pad); a docno listed twice
+ * counts once; a docno no stream record carries contributes nothing and is no
+ * error; ALL records of a docno count (duplicate docids, docno 0 of records
+ * without DOCNO, the negative docnos).  More than 1024 entries in a set is
+ * SME_ELIMIT (the message names the set).
+ * For a term t occurring in the set's records: freq(t) = its occurrences over all
+ * of them, docs(t) = the set's distinct docnos whose records hold it -- the posting
+ * list of t restricted to the set is {(d, tf)} with sum tf = freq and count = docs.
+ * t is KEPT if docs(t) >= min_docs, and min_df <= df(t), and max_df == 0 or df(t) <=
+ * max_df -- df(t) the index's own posting count of t -- and t is not among the
+ * set's exclusion ids x_ids[x_offsets[i] .. x_offsets[i + 1]) (the original query's
+ * terms; host arrays, both NULL for none; -1 excludes nothing; an id outside
+ * [-1, V) is SME_EINVAL, the set named).  The streams hold the DOCNO's tokens, terms
+ * of df 1 with the highest idf: min_df = 2 removes them.
+ * score(t) = (1 + ln freq(t)) * idf(t), one fp64 product of the index's table of
+ * 1 + ln f, continued past the largest tf as far as the batch's largest freq, and
+ * the idf of t's weights: the weight the index would give t in one document that
+ * is the concatenation of the set.  For a set of one docno d it is, bit for bit,
+ * d_weight at the posting (t, d).
+ * A set's kept terms are ordered by score descending, then term id ascending, and
+ * cut to the first m (m == 0: no cut).  Set i's results are term[] / freq[] /
+ * docs[] / score[] at [res_off[i], res_off[i + 1]); nq + 1 offsets, owned by the
+ * index until the next feedback call on it (host memory from the host entry;
+ * device memory from the device entry, with *total = res_off[nq], total may be
+ * NULL).  A feedback call leaves the buffers of every other feature's last call
+ * alone, and the other way round.  nq == 0 is valid.
+ * The host entry takes docnos in host memory.  The device entry takes d_docnos in
+ * DEVICE memory -- sme_query_topk_device's [nq, k] output as it stands, pads
+ * included, with f_offsets[i] = i * k -- while the offsets and the exclusion lists
+ * are host arrays as in the other device entries.
+ * Limits (SME_ELIMIT): 2^31 or more entries in a batch; 2^31 or more stream
+ * positions in one set (the set named); 2^31 or more (set, term) pairs in a batch --
+ * counted as pair slots: min(positions, 3/4 "fb_slots") per set on the on-chip
+ * path plus the pairs of the large path; 2^31 or more stream positions in the sets
+ * that take the large path.  SME_EINVAL, with a message that says which: m,
+ * min_docs, min_df or max_df below 0; offsets that do not ascend from 0; x_ids
+ * without x_offsets; an index without positions, one with K != 1, one without a
+ * query side, a chargram output.  f_offsets is never NULL when nq > 0; docnos may
+ * be NULL only in a batch without an entry.
+ * Evaluation: a docno's records are adjacent, so a document is one run of the
+ * stream.  A workgroup per set counts the set's terms in an LDS hash table of
+ * "fb_slots" entries, document after document; a set with more distinct terms than
+ * 3/4 of the table is counted again by the large path -- one key per position, a
+ * stable sort, a segmented reduce -- which has no size limit but the ones above.
+ * sme_index_feedback_stats reports on the last feedback call on the index:
+ * *positions = the stream positions of the sets' documents, *pairs = the (set,
+ * term) pairs before the filters, *kept = the pairs after the filters and before
+ * the cut, *missing = the distinct docnos of the sets (-1 aside) that no record
+ * carries, *spilled = the sets that took the large path. */
+int sme_index_feedback_terms(sme_index *ix, const int32_t *docnos, const int64_t *f_offsets, int nq,
+                             const int32_t *x_ids, const int64_t *x_offsets, int m, int min_docs, int min_df,
+                             int max_df, const int64_t **res_off, const int32_t **term, const int32_t **freq,
+                             const int32_t **docs, const double **score);
+int sme_index_feedback_terms_device(sme_index *ix, const int32_t *d_docnos, const int64_t *f_offsets, int nq,
+                                    const int32_t *x_ids, const int64_t *x_offsets, int m, int min_docs, int min_df,
+                                    int max_df, void *stream, const int64_t **d_res_off, const int32_t **d_term,
+                                    const int32_t **d_freq, const int32_t **d_docs, const double **d_score,
+                                    int64_t *total);
+int sme_index_feedback_stats(const sme_index *ix, uint64_t *positions, uint64_t *pairs, uint64_t *kept,
+                             uint64_t *missing, uint64_t *spilled);
 
 /* Batched rank(): query q has term ids term_ids[q_offsets[q] .. q_offsets[q+1])
  * in query-token order (duplicates count twice, -1 entries are skipped; an id

@@ -59,6 +59,7 @@ EXPORTS = [
     "sme_index_positions", "sme_query_phrase", "sme_query_phrase_device", "sme_query_phrase_stats",
     "sme_query_near", "sme_query_near_device", "sme_query_near_stats",
     "sme_query_structured", "sme_query_structured_device", "sme_query_structured_stats",
+    "sme_index_feedback_terms", "sme_index_feedback_terms_device", "sme_index_feedback_stats",
 ]
 
 
@@ -166,6 +167,13 @@ def lib():
                                               vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), i64p]
     L.sme_query_structured_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                                              C.POINTER(C.c_uint64)]
+    L.sme_index_feedback_terms.argtypes = [vp, i32p, i64p, C.c_int, i32p, i64p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                           C.POINTER(i64p), C.POINTER(i32p), C.POINTER(i32p), C.POINTER(i32p),
+                                           C.POINTER(f64p)]
+    L.sme_index_feedback_terms_device.argtypes = [vp, vp, i64p, C.c_int, i32p, i64p, C.c_int, C.c_int, C.c_int,
+                                                  C.c_int, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
+                                                  C.POINTER(vp), C.POINTER(vp), i64p]
+    L.sme_index_feedback_stats.argtypes = [vp] + [C.POINTER(C.c_uint64)] * 5
     _lib = L
     return L
 
@@ -530,7 +538,7 @@ class Index:
         _check(lib().sme_index_prepare_wildcards(self._h, C.c_void_p(stream or 0), C.byref(ms)))
         return ms.value
 
-    # ---- the batched query features: n queries in, n + 1 offsets and one to three
+    # ---- the batched query features: n queries in, n + 1 offsets and one to four
     # value columns out (include/sme.h).  The four patterns below are each written
     # once; a feature names its entry, its input dtypes and its column dtypes.
     _CT = {np.int32: C.c_int32, np.int64: C.c_int64, np.uint8: C.c_uint8, np.float64: C.c_double}
@@ -836,6 +844,108 @@ class Index:
         scanned, the Boolean stage's driver entries examined, and the matches
         before the cut."""
         return Index._stats(self._h, lib().sme_query_structured_stats, 4)
+
+    _FEEDBACK_COLS = (np.int32, np.int32, np.int32, np.float64)
+
+    @staticmethod
+    def _feedback_args(f_offsets, exclude, m, min_docs, min_df, max_df):
+        """(arrays to keep alive, the C-ABI's arguments after the docnos): the set
+        offsets, and the exclusion lists -- None, a list of id lists (one per set)
+        or (x_ids, x_offsets) arrays -- as NULL or typed pointers."""
+        nq = len(f_offsets) - 1
+        keep, (foff,) = Index._typed_ptrs([f_offsets], (np.int64,))
+        xid = xoff = None
+        if exclude is not None:
+            a = exclude if isinstance(exclude, tuple) else Index.phrase_arrays(exclude)
+            k2, (xid, xoff) = Index._typed_ptrs(a, (np.int32, np.int64))
+            keep += k2
+        return keep, [foff, nq, xid, xoff, int(m), int(min_docs), int(min_df), int(max_df)]
+
+    def feedback_terms(self, doc_sets, m=20, min_docs=1, min_df=2, max_df=0, exclude=None, arrays=None):
+        """sme_index_feedback_terms: doc_sets = a list of docno lists.  Per set,
+        the terms of those documents' kept streams with freq (occurrences over
+        the set) and docs (the set's documents holding the term), kept if docs >=
+        min_docs, min_df <= df <= max_df (the index's own df; max_df 0: no upper
+        bound) and not among the set's `exclude` ids, scored (1 + ln freq) * idf,
+        ordered by score descending then term id ascending and cut to the first m
+        (0: no cut).  A docno of -1 is skipped, a repeated one counts once, one
+        without a record contributes nothing (include/sme.h).  Returns (res_off
+        int64[n+1], term int32, freq int32, docs int32, score float64).  The
+        index must keep positions (Index.positions).
+        exclude: a list of term id lists, one per set, or (x_ids, x_offsets).
+        arrays: (docnos int32, f_offsets int64[n+1]) instead of doc_sets."""
+        docnos, foff = arrays if arrays is not None else Index.phrase_arrays(doc_sets)
+        keep, (dn,) = Index._typed_ptrs([docnos], (np.int32,))
+        keep2, rest = Index._feedback_args(foff, exclude, m, min_docs, min_df, max_df)
+        return Index._host_call(self._h, lib().sme_index_feedback_terms, [dn] + rest, len(foff) - 1,
+                                Index._FEEDBACK_COLS)
+
+    def feedback_terms_device(self, d_docnos, f_offsets, m=20, min_docs=1, min_df=2, max_df=0, exclude=None,
+                              stream=None):
+        """sme_index_feedback_terms_device: d_docnos = a device pointer of int32
+        docnos, or a contiguous int32 device tensor (anything with data_ptr()) --
+        query_topk_device's output as it stands --, f_offsets the host
+        int64[n+1] offsets of the sets in it.  Returns (device pointer of res_off
+        int64[n+1], of term, freq, docs int32[total], of score float64[total],
+        total); the arrays belong to the index until its next feedback call."""
+        keep, rest = Index._feedback_args(f_offsets, exclude, m, min_docs, min_df, max_df)
+        if hasattr(d_docnos, "data_ptr"):  # a contiguous int32 device tensor
+            d_docnos = d_docnos.data_ptr()
+        return Index._device_call(self._h, lib().sme_index_feedback_terms_device, [C.c_void_p(d_docnos or 0)] + rest,
+                                  stream, Index._FEEDBACK_COLS)
+
+    def feedback_stats(self):
+        """(positions, pairs, kept, missing, spilled) of the last feedback call: the
+        stream positions of the sets' documents, the (set, term) pairs before the
+        filters, the pairs kept before the cut, the sets' docnos without a
+        record, and the sets that took the large path ("fb_slots")."""
+        return Index._stats(self._h, lib().sme_index_feedback_stats, 5)
+
+    def query_feedback(self, term_ids, q_offsets, k=10, fb_docs=10, fb_terms=20, **filters):
+        """Pseudo-relevance feedback: query_topk with k = fb_docs, on the device;
+        feedback_terms_device over those documents, each query's own terms
+        excluded (m = fb_terms; filters: min_docs, min_df, max_df); the expansion
+        terms appended to each query; query_topk of the expanded queries with the
+        original k.  Returns (docno[nq,k], score[nq,k], expanded_term_ids,
+        expanded_offsets).  fb_terms = 0 expands nothing: plain query_topk."""
+        term_ids = np.ascontiguousarray(term_ids, dtype=np.int32)
+        q_offsets = np.ascontiguousarray(q_offsets, dtype=np.int64)
+        nq = len(q_offsets) - 1
+        if nq == 0 or fb_terms <= 0 or fb_docs <= 0:
+            dn, sc = self.query_topk(term_ids, q_offsets, k)
+            return dn, sc, term_ids, q_offsets
+        L, dev = lib(), self.ctx.device
+        bufs = []
+
+        def dalloc(nbytes):
+            p = C.c_void_p()
+            _check(L.sme_device_alloc(dev, max(nbytes, 16), C.byref(p)))
+            bufs.append(p)
+            return p.value
+        try:
+            d_t, d_q = dalloc(term_ids.nbytes), dalloc(q_offsets.nbytes)
+            d_dn, d_sc = dalloc(4 * nq * fb_docs), dalloc(8 * nq * fb_docs)
+            if term_ids.size:
+                memcpy(d_t, term_ids.ctypes.data, term_ids.nbytes)
+            memcpy(d_q, q_offsets.ctypes.data, q_offsets.nbytes)
+            self.query_topk_device(d_t, d_q, nq, fb_docs, d_dn, d_sc)
+            foff = np.arange(nq + 1, dtype=np.int64) * fb_docs
+            d_off, d_term, _, _, _, total = self.feedback_terms_device(d_dn, foff, m=fb_terms,
+                                                                       exclude=(term_ids, q_offsets), **filters)
+            off, terms = np.zeros(nq + 1, np.int64), np.zeros(max(total, 1), np.int32)
+            _d2h(off, d_off, off.nbytes)
+            if total:
+                _d2h(terms, d_term, 4 * total)
+        finally:
+            for p in bufs:
+                L.sme_device_free(p)
+        parts, xoff = [], [0]
+        for i in range(nq):
+            parts += [term_ids[q_offsets[i]:q_offsets[i + 1]], terms[off[i]:off[i + 1]]]
+            xoff.append(xoff[-1] + len(parts[-2]) + len(parts[-1]))
+        expanded, xoff = np.concatenate(parts).astype(np.int32), np.array(xoff, np.int64)
+        dn, sc = self.query_topk(expanded, xoff, k)
+        return dn, sc, expanded, xoff
 
     def reweight(self, n_global, d_df_global=None, stream=None):
         """TF-IDF weights with all-reduced N (and df) of a doc-sharded index."""
@@ -1176,6 +1286,35 @@ class IntDocVectorsForwardIndex:
         """The first k documents (score desc, docno asc) matching get_near's query."""
         _, dn, _, _ = self.index.query_near([getattr(self, "_near", ([], 1, False))], order=1, m=k)
         return [int(d) for d in dn]
+
+    def get_similar(self, docno, terms=25):
+        """More like this: the `terms` best feedback terms of the one document
+        `docno` (Index.feedback_terms with its defaults, so the DOCNO's own tokens
+        are left out) become the query for rank_similar().  Returns the term ids,
+        best first; none if no record carries the docno."""
+        _, ids, _, _, _ = self.index.feedback_terms([[int(docno)]], m=terms)
+        self._similar = (int(docno), [int(t) for t in ids])
+        return self._similar[1]
+
+    def rank_similar(self, k=10):
+        """The first k documents (score desc, docno asc) for get_similar's terms,
+        the source document itself removed."""
+        docno, ids = getattr(self, "_similar", (-1, []))
+        if not ids:
+            return []
+        dn, _ = self.index.query_topk(np.array(ids, np.int32), np.array([0, len(ids)], np.int64), k + 1)
+        return [int(d) for d in dn[0] if d >= 0 and d != docno][:k]
+
+    def rank_feedback(self, text, k=10, fb_docs=10, fb_terms=20):
+        """One query with pseudo-relevance feedback: processContent -> the term
+        lookup (unknown tokens skipped, as getValue skips them) ->
+        Index.query_feedback.  Returns the first k docnos."""
+        ids = [int(t) for t in self.index.lookup(self.index.ctx.process_content(text)) if t >= 0]
+        if not ids:
+            return []
+        dn, _, _, _ = self.index.query_feedback(np.array(ids, np.int32), np.array([0, len(ids)], np.int64), k, fb_docs,
+                                                fb_terms)
+        return [int(d) for d in dn[0] if d >= 0]
 
     def get_structured(self, text):
         """A structured query from a text in parse_structured's syntax:

@@ -11,6 +11,7 @@
 #include <system_error>
 #include <thread>
 
+#include "sme_feedback.hpp"
 #include "sme_internal.hpp"
 
 namespace {
@@ -359,6 +360,12 @@ int sme_set_option(sme_ctx *cx, const char *name, int64_t v) {
     } else if (n == "struct_narrow") {
       range(0, 1);
       cx->opt_struct_narrow = v;
+    } else if (n == "fb_slots") {
+      if (!sme::feedback::legal_slots(v))
+        throw sme::Error(SME_EINVAL, "option " + n + " must be a power of two in [" +
+                                         std::to_string(sme::feedback::kMinSlots) + ", " +
+                                         std::to_string(sme::feedback::kMaxSlots) + "]");
+      cx->opt_fb_slots = v;
     } else {
       throw sme::Error(SME_EINVAL, "unknown option " + n);
     }
@@ -1032,6 +1039,74 @@ int sme_query_near_stats(const sme_index *ix, uint64_t *candidates, uint64_t *ve
   return guard([&] {
     if (!ix || !candidates || !verified || !matches) throw sme::Error(SME_EINVAL, "null argument");
     pass_stats(ix->nq, candidates, verified, matches);
+  });
+}
+
+// Relevance feedback reads the positions of a K = 1 index as phrase queries do, and
+// the query side's document frequencies and idfs.  docnos may be NULL only in a
+// batch without an entry (sme::feedback_terms validates the offsets themselves
+// before anything is read through them).
+static void need_feedback_args(const sme_index *ix, const int32_t *docnos, const int64_t *f_offsets, int nq, int m,
+                               int min_docs, int min_df, int max_df) {
+  need_positions_args(ix, "feedback terms", nullptr, nullptr, 0, 0, 0);
+  if (nq < 0 || (nq > 0 && !f_offsets)) throw sme::Error(SME_EINVAL, "bad argument");
+  if (m < 0) throw sme::Error(SME_EINVAL, "feedback terms: m must be >= 0");
+  if (min_docs < 0) throw sme::Error(SME_EINVAL, "feedback terms: min_docs must be >= 0");
+  if (min_df < 0) throw sme::Error(SME_EINVAL, "feedback terms: min_df must be >= 0");
+  if (max_df < 0) throw sme::Error(SME_EINVAL, "feedback terms: max_df must be >= 0 (0: no upper bound)");
+  if (nq > 0 && f_offsets[nq] > 0 && !docnos) throw sme::Error(SME_EINVAL, "bad argument");
+}
+
+int sme_index_feedback_terms_device(sme_index *ix, const int32_t *d_docnos, const int64_t *f_offsets, int nq,
+                                    const int32_t *x_ids, const int64_t *x_offsets, int m, int min_docs, int min_df,
+                                    int max_df, void *stream, const int64_t **d_res_off, const int32_t **d_term,
+                                    const int32_t **d_freq, const int32_t **d_docs, const double **d_score,
+                                    int64_t *total) {
+  return guard([&] {
+    if (!d_res_off || !d_term || !d_freq || !d_docs || !d_score) throw sme::Error(SME_EINVAL, "null argument");
+    need_feedback_args(ix, d_docnos, f_offsets, nq, m, min_docs, min_df, max_df);
+    set_device(ix->ctx);
+    sme::feedback_terms(ix, d_docnos, true, f_offsets, nq, x_ids, x_offsets, m, min_docs, min_df, max_df,
+                        stream_of(ix->ctx, stream));
+    const sme::TermFreqDocsScores &r = ix->fb;
+    *d_res_off = r.dev_offsets();
+    *d_term = r.dev<sme::TermFreqDocsScores::term>();
+    *d_freq = r.dev<sme::TermFreqDocsScores::freq>();
+    *d_docs = r.dev<sme::TermFreqDocsScores::docs>();
+    *d_score = r.dev<sme::TermFreqDocsScores::score>();
+    if (total) *total = r.total;
+  });
+}
+
+int sme_index_feedback_terms(sme_index *ix, const int32_t *docnos, const int64_t *f_offsets, int nq,
+                             const int32_t *x_ids, const int64_t *x_offsets, int m, int min_docs, int min_df,
+                             int max_df, const int64_t **res_off, const int32_t **term, const int32_t **freq,
+                             const int32_t **docs, const double **score) {
+  return guard([&] {
+    if (!res_off || !term || !freq || !docs || !score) throw sme::Error(SME_EINVAL, "null argument");
+    need_feedback_args(ix, docnos, f_offsets, nq, m, min_docs, min_df, max_df);
+    set_device(ix->ctx);
+    hipStream_t st = ix->ctx->own_stream;
+    sme::feedback_terms(ix, docnos, false, f_offsets, nq, x_ids, x_offsets, m, min_docs, min_df, max_df, st);
+    sme::TermFreqDocsScores &r = ix->fb;
+    r.fetch(st);
+    *res_off = r.h_off.data();
+    *term = r.host<sme::TermFreqDocsScores::term>();
+    *freq = r.host<sme::TermFreqDocsScores::freq>();
+    *docs = r.host<sme::TermFreqDocsScores::docs>();
+    *score = r.host<sme::TermFreqDocsScores::score>();
+  });
+}
+
+int sme_index_feedback_stats(const sme_index *ix, uint64_t *positions, uint64_t *pairs, uint64_t *kept,
+                             uint64_t *missing, uint64_t *spilled) {
+  return guard([&] {
+    if (!ix || !positions || !pairs || !kept || !missing || !spilled) throw sme::Error(SME_EINVAL, "null argument");
+    *positions = ix->fb_positions;
+    *pairs = ix->fb_pairs;
+    *kept = ix->fb_kept;
+    *missing = ix->fb_missing;
+    *spilled = ix->fb_spilled;
   });
 }
 

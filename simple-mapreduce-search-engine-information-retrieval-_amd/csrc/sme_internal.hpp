@@ -75,6 +75,7 @@ struct sme_ctx {
   int64_t opt_bool_driver = 0;    // "bool_driver": 0 = the required group with the fewest postings drives, 1 = the first
   int64_t opt_positions = 0;      // "positions": 1 = a K = 1 build keeps every record's term stream (phrase queries)
   int64_t opt_struct_narrow = 1;  // "struct_narrow": 1 = a structured query's term groups cut its operator leaves' candidates
+  int64_t opt_fb_slots = 4096;    // "fb_slots": entries of relevance feedback's on-chip table (16..4096, a power of two)
   int64_t opt_corpus_keep = int64_t(16) << 30;  // "corpus_keep_bytes": host-corpus builds keep their device copy
                                                 // (no hipMalloc next build) only up to this size
   // pinned host staging of device -> host record copies into pageable caller
@@ -199,6 +200,11 @@ struct sme_index {
   sme::DocScores sq;
   uint64_t sq_leaves = 0;
   sme::DocFreqScores sv;
+  // relevance feedback (sme_feedback.hip): the last call's result and its counts --
+  // stream positions of the sets, (set, term) pairs before the filters, pairs kept
+  // before the cut, set docnos without a record, sets that took the large path
+  sme::TermFreqDocsScores fb;
+  uint64_t fb_positions = 0, fb_pairs = 0, fb_kept = 0, fb_missing = 0, fb_spilled = 0;
   // stage timings of the build that produced this index (ms)
   std::vector<std::pair<std::string, float>> profile;
   ~sme_index() { ctx->live_indexes--; }  // members (pooled buffers) are released after this body
@@ -209,7 +215,7 @@ struct sme_index {
                            &d_wgterm, &d_wx_in, &d_wx_plan, &d_wx_choff, &d_wx_moff, &d_wx_scan, &d_ps_off, &d_ps_terms,
                            &d_ps_docno, &d_nq_lut})
       b->pool = &c->pool;
-    for (sme::ResultSet *r : std::initializer_list<sme::ResultSet *>{&wx, &fz, &bq, &pq, &nq, &sq, &sv})
+    for (sme::ResultSet *r : std::initializer_list<sme::ResultSet *>{&wx, &fz, &bq, &pq, &nq, &sq, &sv, &fb})
       r->bind(&c->pool);
   }
 };
@@ -407,6 +413,17 @@ struct NarrowSpec {
 void near_pass(sme_index *ix, DocFreqScores &out, const int32_t *term_ids, const int64_t *q_offsets,
                const int32_t *widths, const uint8_t *kinds, int nq, int order, int m, const NarrowSpec *narrow,
                hipStream_t st);
+// the index's scorer table 1 + ln(f) (d_nq_lut) grown to n entries at least, by the
+// build's own expression (sme_near.hip); `st` is synchronised when it grows
+void grow_score_lut(sme_index *ix, int64_t n, hipStream_t st);
+// relevance feedback (sme_feedback.hip): n sets of docnos (device memory if
+// on_device, else a host array; the offsets and the optional exclusion lists: host
+// arrays, validated here) over the positions a K = 1 build kept -> per set its kept
+// terms with freq, docs and score, by score descending then term ascending, cut to
+// m: ix->fb and the fb_ counts
+void feedback_terms(sme_index *ix, const int32_t *docnos, bool on_device, const int64_t *f_offsets, int n,
+                    const int32_t *x_ids, const int64_t *x_offsets, int m, int min_docs, int min_df, int max_df,
+                    hipStream_t st);
 // structured queries (sme_structq.hip): nq queries of required / excluded groups of
 // leaves -- a term, or an ordered / unordered window over terms (host arrays,
 // validated here) -> per query the matching documents and scores, ordered and cut

@@ -160,6 +160,17 @@ __global__ void k_near_doc_span(const int64_t *__restrict__ ps_off, const int32_
 }
 }  // namespace
 
+void grow_score_lut(sme_index *ix, int64_t n, hipStream_t st) {
+  if (n <= ix->nq_lut_n) return;
+  std::vector<double> lut((size_t)n, 0.0);
+  for (int64_t i = 1; i < n; i++) lut[(size_t)i] = 1.0 + log((double)i);
+  double *d = ix->d_nq_lut.as<double>((size_t)n);
+  ix->nq_lut_n = 0;
+  SME_HIP(hipMemcpyAsync(d, lut.data(), lut.size() * sizeof(double), hipMemcpyHostToDevice, st));
+  SME_HIP(hipStreamSynchronize(st));  // (lut leaves scope)
+  ix->nq_lut_n = n;
+}
+
 void query_near(sme_index *ix, const int32_t *term_ids, const int64_t *q_offsets, const int32_t *widths,
                 const uint8_t *kinds, int nq, int order, int m, hipStream_t st) {
   int bad = -1;
@@ -210,15 +221,7 @@ void near_pass(sme_index *ix, DocFreqScores &out, const int32_t *term_ids, const
         distinct += std::find(term_ids + q_offsets[i], term_ids + s, term_ids[s]) == term_ids + s;
       lut_n = std::max(lut_n, std::min((int64_t)distinct * ix->max_tf, ix->nq_max_span) + 1);
     }
-    if (lut_n > ix->nq_lut_n) {
-      std::vector<double> lut((size_t)lut_n, 0.0);
-      for (int64_t i = 1; i < lut_n; i++) lut[(size_t)i] = 1.0 + log((double)i);
-      double *d = ix->d_nq_lut.as<double>((size_t)lut_n);
-      ix->nq_lut_n = 0;
-      SME_HIP(hipMemcpyAsync(d, lut.data(), lut.size() * sizeof(double), hipMemcpyHostToDevice, st));
-      SME_HIP(hipStreamSynchronize(st));  // (lut leaves scope)
-      ix->nq_lut_n = lut_n;
-    }
+    grow_score_lut(ix, lut_n, st);
     lut_n = ix->nq_lut_n;
   }
   DevBuf ovb;

@@ -1,5 +1,5 @@
 // sme_result.hpp -- what a batched query call leaves on the index: n + 1 offsets
-// and up to three value columns of `total` entries, query i's values at
+// and up to four value columns of `total` entries, query i's values at
 // [off[i], off[i + 1]), beside the call's counts.
 //
 // Ownership: the device arrays and the host mirrors belong to the index until the
@@ -21,7 +21,7 @@
 namespace sme {
 
 struct ResultSet {
-  static constexpr int kMaxCols = 3;
+  static constexpr int kMaxCols = 4;
   struct Column {
     DevBuf d;                // [total] elements of esize bytes
     size_t esize = 0;        // 0: no such column
@@ -96,6 +96,9 @@ struct DocScores : ResultOf<int32_t, double> {  // Boolean retrieval, structured
 };
 struct DocFreqScores : ResultOf<int32_t, int32_t, double> {  // phrase / proximity pass (sme_phrase_pass.hpp)
   enum { docno, freq, score };  // matching documents; the query's count in each; their scores
+};
+struct TermFreqDocsScores : ResultOf<int32_t, int32_t, int32_t, double> {  // relevance feedback (sme_feedback.hip)
+  enum { term, freq, docs, score };  // a set's terms; their occurrences; the set's documents holding them; their scores
 };
 
 }  // namespace sme
