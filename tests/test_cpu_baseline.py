@@ -71,6 +71,20 @@ def test_cpuopt_ascii_fast_path_edges():
     _check(b"".join(recs), sorted("E%02d" % i for i in range(40)), 3)
 
 
+@pytest.mark.parametrize("threads", [1, 4])
+@pytest.mark.parametrize("which", ["rule_words", "families"])
+def test_cpuopt_stem_words(which, threads):
+    """Every stemmer rule, and terms with over a hundred raw forms in three
+    spellings (tests/stem_words.py), through cpu-opt's ASCII fast path and its
+    per-thread stem caches."""
+    import stem_words as S
+    if which == "rule_words":
+        corpus, ids = S.records_of(S.rule_words() + S.length_edges())
+    else:
+        corpus, ids = S.family_corpus()
+    _check(corpus, list(ids), threads)
+
+
 def test_cpuopt_from_csr_matches_built_index():
     """The cpu-opt rank() over an index wrapped from CSR arrays (bench.py's
     full-index CPU query leg) answers like the cpu-opt index built from text."""
