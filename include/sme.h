@@ -121,6 +121,10 @@ void sme_destroy(sme_ctx *ctx);
  *                   docids ascend in file order; 0: every raw token through the general path
  *   "sort_digit_bits"  most bits per digit of the term sort's LSD passes, 6..11, or 0 (default:
  *                   11 -- two passes for up to 2^22 terms -- and 8 past 2^30 pairs)
+ *   "term_off_tables"  1 (default): the CSR offsets are read out of the term sort's own offset
+ *                   tables, and its last pass stores the sorted keys only when a later step reads
+ *                   them (the df idf modes, a tf above 1023); 0: the keys are always stored and the
+ *                   offsets found by a pass over them
  *   "docid_split"   1 (default): with docid terms (K4b) that push the term ids past 22 bits
  *                   while the word terms need fewer, each record's docid pair is kept beside
  *                   the sort of word-rank keys and merged into the CSR after it; 2: whenever

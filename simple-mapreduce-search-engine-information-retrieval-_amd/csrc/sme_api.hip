@@ -334,6 +334,9 @@ int sme_set_option(sme_ctx *cx, const char *name, int64_t v) {
     } else if (n == "sort_digit_bits") {
       if (v != 0) range(6, 11);
       cx->opt_sort_bits = v;
+    } else if (n == "term_off_tables") {
+      range(0, 1);
+      cx->opt_term_off_tables = v;
     } else if (n == "docid_split") {
       range(0, 2);
       cx->opt_docid_split = v;

@@ -2333,7 +2333,7 @@ __device__ __forceinline__ int64_t words_below(int64_t j, const int64_t *drank, 
   const int64_t x = drank[j] - j;
   return x < Vw ? off[wrank[x]] - (int64_t)ws[x].x : Pw;
 }
-// docid pair q -> its CSR slot (docno / tf / weight / key)
+// docid pair q -> its CSR slot (docno / tf / weight, and the key unless nullptr)
 __global__ void k_docid_place(const uint32_t *dk, const uint32_t *dv, int64_t Nd, const int64_t *drank,
                               const int64_t *wrank, int64_t Vw, const uint2 *ws, const int64_t *off, int64_t Pw,
                               int64_t dmin, uint32_t F, int32_t *docno, int32_t *tf, uint32_t *key, const double *lut,
@@ -2344,7 +2344,7 @@ __global__ void k_docid_place(const uint32_t *dk, const uint32_t *dv, int64_t Nd
     const uint32_t v = dv[q];
     docno[p] = (int32_t)((int64_t)(v / F) + dmin);
     tf[p] = (int32_t)(v % F);
-    key[p] = (uint32_t)drank[j];
+    if (key) key[p] = (uint32_t)drank[j];
     if (w) w[p] = __dmul_rn(lut[v % F], idf);
   }
 }
@@ -4343,23 +4343,30 @@ vocab_again:  // (a docid term equal to a word term: the general path, from here
       weights_fused = true;
     }
     const double idf_r = log10((double)(std::max<int64_t>(nR, 0) / 1));
-    key_s = term_sort(p_term, v32, key_s, v32s, sort_nrec, sort_reg, sort_xoff, Pw, tbits, dmin, F, docno_d, tf_d, rscr,
-                      st, wf ? (const double *)ix->d_lut.p : nullptr, idf_r, wf, sort_bits, xw, P, ai.rec_val,
-                      ai.tf_shift);
+    // term_off_tables: the word terms' offsets come out of the sort's own offset
+    // table, and the sorted keys are written only when something below reads them
+    // (k_weights in the df idf modes, the composite tf sort past kTfSortMaxTf)
+    const bool off_tables = cx->opt_term_off_tables != 0;
+    const bool want_keys = !(off_tables && weights_fused && max_tf <= kTfSortMaxTf);
     off = ix->d_off.as<int64_t>(Vi + 1);
     SME_HIP(hipMemsetAsync(off, 0, (Vi + 1) * sizeof(int64_t), st));
+    key_s = term_sort(p_term, v32, key_s, v32s, sort_nrec, sort_reg, sort_xoff, Pw, tbits, dmin, F, docno_d, tf_d, rscr,
+                      st, wf ? (const double *)ix->d_lut.p : nullptr, idf_r, wf, sort_bits, xw, P, ai.rec_val,
+                      ai.tf_shift, off_tables ? off : nullptr, split ? Vw : Vi, Vi, want_keys);
     if (!split) {
-      hipLaunchKernelGGL(k_term_offsets<false>, dim3(grid_for(P)), dim3(256), 0, st, key_s, P, off, Vi);
+      if (!off_tables)
+        hipLaunchKernelGGL(k_term_offsets<false>, dim3(grid_for(P)), dim3(256), 0, st, key_s, P, off, Vi);
     } else {
-      // word terms' offsets over the sorted keys (the docid slots are holes), then
-      // the docid terms' offsets and their pairs in the holes
-      hipLaunchKernelGGL(k_term_offsets<true>, dim3(grid_for(P)), dim3(256), 0, st, key_s, P, off, Vi);
+      // word terms' offsets (over the sorted keys, the docid slots being holes, when
+      // not from the tables), then the docid terms' offsets and their pairs in the holes
+      if (!off_tables)
+        hipLaunchKernelGGL(k_term_offsets<true>, dim3(grid_for(P)), dim3(256), 0, st, key_s, P, off, Vi);
       hipLaunchKernelGGL(k_docid_off, dim3(grid_for(Vd)), dim3(256), 0, st, dk, Nd, Vd, (const int64_t *)drank,
                          (const int64_t *)wrank_all, Vw, xw, Pw, off);
       if (Nd > 0)
         hipLaunchKernelGGL(k_docid_place, dim3(grid_for(Nd)), dim3(256), 0, st, dk, dv, Nd, (const int64_t *)drank,
-                           (const int64_t *)wrank_all, Vw, xw, off, Pw, dmin, F, docno_d, tf_d, key_s,
-                           wf ? (const double *)ix->d_lut.p : nullptr, idf_r, wf);
+                           (const int64_t *)wrank_all, Vw, xw, off, Pw, dmin, F, docno_d, tf_d,
+                           want_keys ? key_s : nullptr, wf ? (const double *)ix->d_lut.p : nullptr, idf_r, wf);
     }
     SME_CHECK_LAUNCH();
   } else {

@@ -60,6 +60,7 @@ struct sme_ctx {
   int64_t opt_raw_load_pct = 40;  // "raw_load_pct": raw-vocabulary table load of the next build (10..90)
   int64_t opt_docid_terms = 1;    // "docid_terms": docid terms beside the word vocabulary (K4b; 0 = general path)
   int64_t opt_sort_bits = 0;      // "sort_digit_bits": most bits per digit of the term sort's LSD passes (6..11; 0 auto)
+  int64_t opt_term_off_tables = 1;  // "term_off_tables": 1 = CSR offsets from the term sort's tables (sorted keys only when read), 0 = from the sorted keys
   int64_t opt_docid_split = 1;    // "docid_split": docid pairs beside the term sort (K6b): 1 past 22 merged id bits, 2 whenever the words need fewer, 0 never
   int64_t opt_cand_cap = 1024;    // "cand_cap": candidate list per query of k_query_win (1..2048; >= 1024: at least 16 k)
   int64_t opt_seed_m = 64;        // "seed_m": seed postings per term (k_query_seed; 0 = no seed)
@@ -286,7 +287,11 @@ uint32_t *term_sort(uint32_t *k0, uint32_t *v0, uint32_t *k1, uint32_t *v1, int6
                     const int64_t *xoff, int64_t P, int bits, int64_t dmin, uint32_t F, int32_t *docno, int32_t *tf,
                     uint32_t *counts, hipStream_t st, const double *lut = nullptr, double idf = 0.0,
                     double *w = nullptr, int maxbits = 11, const uint2 *xw = nullptr, int64_t Pout = 0,
-                    const uint32_t *rec_val = nullptr, int tf_shift = 0);
+                    const uint32_t *rec_val = nullptr, int tf_shift = 0, int64_t *off_out = nullptr, int64_t V = 0,
+                    int64_t vend = 0, bool write_keys = true);
+// (off_out != nullptr: the first slot of every term id < V that has pairs, read
+// from the last pass's offset table, and off_out[vend ? vend : V] = the pair count;
+// write_keys false: the sorted keys are not stored)
 // (rec_val != nullptr, gather mode: the regions hold one packed word per pair,
 // term | tf << tf_shift, and rec_val[i] = record i's base value; v0 is then read
 // by no pass, and written only when there are three passes or more)

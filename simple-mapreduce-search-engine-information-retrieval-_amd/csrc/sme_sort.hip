@@ -19,8 +19,10 @@
 //                tile's digit-sorted order, stages keys and then values in
 //                LDS in that order, and writes them out as contiguous runs
 //                per digit (offset(tile, digit) + slot - digit's first slot).
-// The last pass writes the sorted keys and unpacks the packed values
-// ((docno - dmin) * F + tf) straight into the CSR's docno / tf arrays.  After
+// The last pass writes the sorted keys (unless the caller reads none) and unpacks
+// the packed values ((docno - dmin) * F + tf) straight into the CSR's docno / tf
+// arrays; k_rs_term_off reads the terms' first slots out of that pass's offset
+// table, so no pass over the sorted keys is needed for the CSR offsets.  After
 // the single-pass aggregation the first pass gathers its items from the
 // records' regions, one packed word per pair (Gather).
 #include <hip/hip_runtime.h>
@@ -43,6 +45,7 @@ constexpr int kRsMaxBins = 1 << kRsMaxBits;
 constexpr int kRsBPT = kRsMaxBins / kRsNT;  // digits per thread in the scatter's tile scan
 constexpr int kRsGroups = 1024;             // most tile groups of the column scan
 constexpr int kRsScanSums = 1024;           // device scan of the (digit, group) sums: its tile sums
+constexpr int kRsOffTiles = 16;             // tiles per workgroup of k_rs_term_off (<= 32: one mask bit each)
 
 // Tile groups of the column scan: at least 4 tiles a group, so the one-block
 // scan over (digit, group) sums stays short for small sorts; a multiple of 16
@@ -109,6 +112,10 @@ __device__ __forceinline__ int64_t gather_table(const Gather &g, int64_t x0, int
 }
 __device__ __forceinline__ int64_t gather_at(const Gather &g, int64_t x, int &j, const int64_t *gx, const int64_t *gdl,
                                              int64_t rec0, uint32_t *jr = nullptr) {
+#ifdef SME_RS_GATHER_CEIL  // (experiment, timing only: no walk.  Right only where the regions are one dense run)
+  if (jr) *jr = 0u;
+  return x + gdl[0];
+#endif
   while (j < kGRec - 1 && x >= gx[j + 1]) j++;
   if (x < gx[j + 1]) {
     if (jr) *jr = (uint32_t)j;
@@ -260,8 +267,9 @@ __global__ __launch_bounds__(kRsNT) void k_rs_colscan(uint32_t *__restrict__ cou
 }
 
 // (PACK: the first pass over packed words, see Gather; its own instantiation, so
-// the other passes' code is what it is without it)
-template <bool LAST, bool PACK>
+// the other passes' code is what it is without it.  KEYS false: a last pass that
+// stores no sorted keys, for callers that take the offsets from k_rs_term_off)
+template <bool LAST, bool PACK, bool KEYS = true>
 __global__ __launch_bounds__(kRsNT) void k_rs_scatter(const uint32_t *__restrict__ key, const uint32_t *__restrict__ val,
                                                       int64_t P, int shift, int nbits,
                                                       const uint32_t *__restrict__ offs, uint32_t *__restrict__ okey,
@@ -418,8 +426,8 @@ __global__ __launch_bounds__(kRsNT) void k_rs_scatter(const uint32_t *__restrict
       if (LAST && xw) {  // K6b: word kk's docid shift and merged id
         const uint2 x = xw[kk];
         dst[j] += x.x;
-        okey[dst[j]] = x.y;
-      } else {
+        if (KEYS) okey[dst[j]] = x.y;
+      } else if (KEYS) {
         okey[dst[j]] = kk;
       }
     }
@@ -444,6 +452,125 @@ __global__ __launch_bounds__(kRsNT) void k_rs_scatter(const uint32_t *__restrict
         oval[dst[j]] = vv;
       }
     }
+  }
+}
+
+// First output slot of every term, from the last pass's tables (no sorted-key
+// array).  The last pass's input is sorted by the key's low `shift` bits L (the
+// earlier passes are stable), so the items of one L are one contiguous segment.
+// Term (d, L) = d << shift | L starts at
+//   offs[t][d] + #{items of tile t before position s whose digit is d}
+// with s the segment's first position and t its tile: every item with a smaller
+// digit, plus the digit-d items before the segment.  One workgroup per
+// kRsOffTiles tiles: one lane per tile finds with two key loads whether the tile
+// holds a segment start (most do not: at most 2^shift do, and c2 has 45 k tiles).
+// The workgroup lists the starts of each such tile in order and walks them with
+// a running digit histogram in LDS, writing all 2^nbits entries of each
+// segment: O(8192 * tiles with a start + 2^bits) work, no global atomics.
+// shift == 0 (one pass): a single segment, the entries are offs[0][d] and no
+// key is read.
+// An id below V without pairs gets the slot where its pairs would start if some
+// id shares its low part L, and is left as it was otherwise (the build zeroes
+// off[] first; its ids all have pairs).  xw (K6b): word k's entry goes to
+// off[xw[k].y], shifted by xw[k].x.  off[vend] = pend.
+__global__ __launch_bounds__(kRsNT) void k_rs_term_off(const uint32_t *__restrict__ key, int64_t P, int shift, int nbits,
+                                                       const uint32_t *__restrict__ offs, int64_t V,
+                                                       const uint2 *__restrict__ xw, int64_t *__restrict__ off,
+                                                       int64_t vend, int64_t pend) {
+  __shared__ uint32_t ks[kRsTile];
+  __shared__ uint16_t sp[kRsTile];  // the tile's segment starts, ascending
+  __shared__ uint32_t hist[kRsMaxBins];
+  __shared__ uint32_t rc[kRsIPL * kRsWaves + 1];
+  __shared__ uint32_t act;  // bit i: tile blockIdx.x * kRsOffTiles + i holds a segment start
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int nbins = 1 << nbits;
+  const uint32_t mask = (uint32_t)nbins - 1u;
+  const uint32_t lmask = (1u << shift) - 1u;
+  if (blockIdx.x == 0 && tid == 0) off[vend] = pend;
+  if (P <= 0) return;
+  int64_t tile = 0;
+  auto emit = [&](uint32_t L) {  // the entries of segment L, which starts at the histogram's position
+    for (int d = tid; d < nbins; d += kRsNT) {
+      const uint64_t k = ((uint64_t)d << shift) | L;
+      if (k < (uint64_t)V) {
+        const int64_t o = (int64_t)offs[tile * nbins + d] + hist[d];
+        if (xw) {
+          const uint2 x = xw[k];
+          off[x.y] = o + x.x;
+        } else {
+          off[k] = o;
+        }
+      }
+    }
+  };
+  if (shift == 0) {
+    for (int b = tid; b < nbins; b += kRsNT) hist[b] = 0;
+    __syncthreads();
+    emit(0u);
+    return;
+  }
+  // low parts ascend: a tile holds a start iff it is the first, or the item
+  // before it and its last item differ
+  if (tid == 0) act = 0u;
+  __syncthreads();
+  if (tid < kRsOffTiles) {
+    const int64_t a0 = ((int64_t)blockIdx.x * kRsOffTiles + tid) * kRsTile;
+    if (a0 < P) {
+      const int64_t last = min(a0 + kRsTile, P) - 1;
+      if (a0 == 0 || (key[a0 - 1] & lmask) != (key[last] & lmask)) atomicOr(&act, 1u << tid);
+    }
+  }
+  __syncthreads();
+  const uint64_t lt = (1ull << lane) - 1ull;
+  for (uint32_t todo = act; todo != 0u; todo &= todo - 1u) {
+    tile = (int64_t)blockIdx.x * kRsOffTiles + (__ffs(todo) - 1);
+    const int64_t t0 = tile * kRsTile;
+    const int n = (int)min((int64_t)kRsTile, P - t0);
+    const uint32_t lprev = t0 > 0 ? key[t0 - 1] & lmask : 0u;
+    for (int b = tid; b < nbins; b += kRsNT) hist[b] = 0;
+    for (int p = tid; p < n; p += kRsNT) ks[p] = key[t0 + p];
+    __syncthreads();
+    uint32_t mine = 0;  // bit j: item j * kRsNT + tid is a start
+#pragma unroll
+    for (int j = 0; j < kRsIPL; j++) {
+      const int p = j * kRsNT + tid;
+      bool f = false;
+      if (p < n) f = (ks[p] & lmask) != (p > 0 ? ks[p - 1] & lmask : lprev) || (p == 0 && t0 == 0);
+      const uint64_t b = (uint64_t)__ballot(f);
+      if (f) mine |= 1u << j;
+      if (lane == 0) rc[j * kRsWaves + w] = (uint32_t)__popcll(b);
+    }
+    __syncthreads();
+    if (w == 0) {  // exclusive scan of the kRsIPL * kRsWaves = 128 (round, wave) counts: position order
+      const uint32_t a = rc[2 * lane], b = rc[2 * lane + 1];
+      uint32_t incl = a + b;
+      for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t u = __shfl_up(incl, o, 64);
+        if (lane >= o) incl += u;
+      }
+      rc[2 * lane] = incl - a - b;
+      rc[2 * lane + 1] = incl - b;
+      if (lane == 63) rc[kRsIPL * kRsWaves] = incl;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < kRsIPL; j++) {
+      const bool f = (mine >> j) & 1u;
+      const uint64_t b = (uint64_t)__ballot(f);
+      if (f) sp[rc[j * kRsWaves + w] + (uint32_t)__popcll(b & lt)] = (uint16_t)(j * kRsNT + tid);
+    }
+    __syncthreads();
+    const int ns = (int)rc[kRsIPL * kRsWaves];
+    int pos = 0;
+    for (int si = 0; si < ns; si++) {
+      const int s = sp[si];
+      for (int p = pos + tid; p < s; p += kRsNT) atomicAdd(&hist[(ks[p] >> shift) & mask], 1u);
+      __syncthreads();
+      emit(ks[s] & lmask);
+      __syncthreads();
+      pos = s;
+    }
+    __syncthreads();  // (the next tile rewrites ks, hist, rc and sp)
   }
 }
 
@@ -727,11 +854,25 @@ void rs_scan(uint32_t *gsum, int64_t n, uint32_t *sums, hipStream_t st) {
 // rec_val (gather mode only): the regions hold packed words, term | tf << tf_shift,
 // and rec_val[i] is record i's base value; the first pass then reads k0 alone
 // (v0 may be nullptr unless a third pass writes it: term_sort_passes).
+// off_out: the CSR offsets from the last pass's tables (k_rs_term_off): V = the
+// number of term ids sorted, off_out[vend ? vend : V] = the pair count (Pout with
+// xw, whose entries go to the merged ids).  write_keys false: the last pass stores
+// no keys and the returned buffer's contents are unspecified.
 uint32_t *term_sort(uint32_t *k0, uint32_t *v0, uint32_t *k1, uint32_t *v1, int64_t nrec, const int64_t *reg,
                     const int64_t *xoff, int64_t P, int bits, int64_t dmin, uint32_t F, int32_t *docno, int32_t *tf,
                     uint32_t *counts, hipStream_t st, const double *lut, double idf, double *w, int maxbits,
-                    const uint2 *xw, int64_t Pout, const uint32_t *rec_val, int tf_shift) {
-  if (P <= 0) return k0;
+                    const uint2 *xw, int64_t Pout, const uint32_t *rec_val, int tf_shift, int64_t *off_out, int64_t V,
+                    int64_t vend, bool write_keys) {
+  if (vend <= 0) vend = V;
+  const int64_t pend = xw ? Pout : std::max<int64_t>(P, 0);
+  if (P <= 0) {
+    if (off_out) {
+      hipLaunchKernelGGL(k_rs_term_off, dim3(1), dim3(kRsNT), 0, st, nullptr, 0, 0, 1, nullptr, V, xw, off_out, vend,
+                         pend);
+      SME_CHECK_LAUNCH();
+    }
+    return k0;
+  }
   if (P > 0xFFFFFFFFll) throw Error(SME_ELIMIT, "term sort of more than 2^32 pairs");
   bits = std::max(bits, 1);
   maxbits = std::min(std::max(maxbits, 1), kRsMaxBits);
@@ -764,17 +905,21 @@ uint32_t *term_sort(uint32_t *k0, uint32_t *v0, uint32_t *k1, uint32_t *v1, int6
     rs_scan(gsum, (int64_t)nbins * G, gsum + kRsMaxBins * kRsGroups, st);
     hipLaunchKernelGGL(k_rs_colscan, dim3(G), dim3(kRsNT), 0, st, counts, ntiles, nbins, tpg, G, gsum);
     const unsigned sgrid = (unsigned)(8 * ((ntiles + 7) / 8));  // see the XCD tile order in k_rs_scatter
-    if (last && xw)  // K6b: the docid pairs' slots stay keyed 0xFFFFFFFF (k_term_offsets<true> skips them)
+    if (last && xw && write_keys)  // K6b: the docid pairs' slots stay keyed 0xFFFFFFFF (k_term_offsets<true> skips them)
       SME_HIP(hipMemsetAsync(k1, 0xFF, (size_t)Pout * sizeof(uint32_t), st));
     const bool pack = g.reg != nullptr && g.rval != nullptr;
-    auto *scatter = last ? (pack ? k_rs_scatter<true, true> : k_rs_scatter<true, false>)
-                         : (pack ? k_rs_scatter<false, true> : k_rs_scatter<false, false>);
+    auto *scatter = !last        ? (pack ? k_rs_scatter<false, true> : k_rs_scatter<false, false>)
+                    : write_keys ? (pack ? k_rs_scatter<true, true> : k_rs_scatter<true, false>)
+                                 : (pack ? k_rs_scatter<true, true, false> : k_rs_scatter<true, false, false>);
     if (last)
       hipLaunchKernelGGL(scatter, dim3(sgrid), dim3(kRsNT), 0, st, k0, v0, P, shift, nb, counts, k1, nullptr, docno, tf,
                          dmin, F, g, lut, idf, w, xw);
     else
       hipLaunchKernelGGL(scatter, dim3(sgrid), dim3(kRsNT), 0, st, k0, v0, P, shift, nb, counts, k1, v1, nullptr,
                          nullptr, dmin, F, g, nullptr, 0.0, nullptr, nullptr);
+    if (last && off_out)  // (counts and this pass's input keys are still intact)
+      hipLaunchKernelGGL(k_rs_term_off, dim3(shift == 0 ? 1u : (unsigned)((ntiles + kRsOffTiles - 1) / kRsOffTiles)),
+                         dim3(kRsNT), 0, st, k0, P, shift, nb, counts, V, xw, off_out, vend, pend);
     SME_CHECK_LAUNCH();
     std::swap(k0, k1);
     std::swap(v0, v1);
