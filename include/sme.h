@@ -161,6 +161,12 @@ void sme_destroy(sme_ctx *ctx);
  *                   table of one document set, a power of two in 16..4096 (default 4096, 48 KiB
  *                   of LDS: two workgroups fit a CU); a set with more than 3/4 of that many
  *                   distinct terms takes the large path.  Results are the same
+ *   "merge_tile"    sme_index_merge: docno-order postings per tile of its n-way merge, a multiple
+ *                   of 64 in 64..2048 (default 1024: 26 KiB of LDS per workgroup).  Results are
+ *                   the same
+ *   "merge_append"  sme_index_merge: 1 (default) inputs whose docno ranges are pairwise disjoint
+ *                   are laid end to end without merging, 0 every call takes the general merge.
+ *                   Results are the same
  * Unknown names and out-of-range values are SME_EINVAL. */
 int sme_set_option(sme_ctx *ctx, const char *name, int64_t value);
 
@@ -444,7 +450,8 @@ int sme_query_boolean_stats(const sme_index *ix, uint64_t *candidates, uint64_t 
  * = term positions over all of them, *bytes = device memory they take; all three
  * 0 for an index that keeps none: one built without the option or with K >= 2, a
  * chargram output, and every index from sme_index_from_records* or
- * sme_merge_pieces -- positions cannot be added to an index later. */
+ * sme_merge_pieces -- positions cannot be added to an index later; sme_index_merge
+ * carries its inputs' over. */
 int sme_index_positions(const sme_index *ix, uint64_t *records, uint64_t *positions, uint64_t *bytes);
 
 /* Phrase queries (no reference counterpart; the reference answers a phrase of m
@@ -830,6 +837,49 @@ int sme_index_pack_pieces(sme_index *ix, int world, void *d_out, uint64_t *sizes
 int sme_index_record_docnos(sme_index *ix, const int32_t **d_docno, int64_t *n);
 int sme_merge_pieces(sme_ctx *ctx, const void *d_blobs, const uint64_t *sizes, int n, void *stream,
                      sme_index **out);
+
+/* Merge n indexes of ctx (1 <= n <= 64) into one new, full index: what one build
+ * of the inputs' corpora laid end to end gives, in every array.  The inputs are
+ * read only and stay valid; they may be built, loaded from records or themselves
+ * merged, in any mix, and are taken in the order given, as the map tasks of one
+ * job in that order.  THEY MUST HAVE BEEN NUMBERED WITH ONE DOCNO MAPPING: docnos
+ * are compared as they are, and nothing here can check where they came from.
+ *   vocabulary  the union of the inputs' term strings in TermDF (String.compareTo)
+ *               order, equal strings one term;
+ *   postings    per term the inputs' lists merged by docno; a docno several inputs
+ *               hold (a docid in two of them, docno 0, negative docnos of unmapped
+ *               docids) is one posting with the tfs summed, as MyReducer.reduce and
+ *               the build's duplicate-docno merge do (a sum >= 2^24 is SME_ELIMIT);
+ *               the reduce order is that list stably sorted by tf descending;
+ *   weights     N = the sum of the inputs' N, true df = the merged list's length,
+ *               then the weights of sme_index_reweight(N) under ctx's idf mode.  An
+ *               input's own earlier sme_index_reweight is NOT carried over;
+ *   doc counter the inputs' lists back to back, every input's map-task starts kept
+ *               (a built input is one task), so the " " record serializes as the
+ *               reference job over those map tasks writes it.  As for a loaded
+ *               index, sme_index_record_docnos / sme_index_pack_pieces on the
+ *               result return SME_EINVAL;
+ *   positions   kept if every input that has records keeps them ("positions"): the
+ *               records' streams in docno-ascending order (equal docnos: input
+ *               order, then the order inside the input), term ids rewritten to the
+ *               merged ids; more than 2^31 - 1 stream positions is SME_ELIMIT.
+ *               Otherwise the result keeps none and the position entry points
+ *               refuse it as they refuse any index without them.
+ * The query side and the wildcard table are built on first use, as for any index.
+ * Refused before any per-term work, the message naming the input's place in the
+ * list: n out of range, a null input, an input of another context, a records-only
+ * input (sme_merge_pieces output), a chargram output (all SME_EINVAL); the context
+ * or an input with K != 1 is SME_ENOTIMPL ("merging K >= 2 indexes").  n = 1 gives
+ * a copy; inputs without records or terms are legal anywhere in the list.
+ * sme_last_build_profile then holds the merger's stages (terms, postings,
+ * tf_order, weights, positions, total).  stream NULL = the context's stream. */
+int sme_index_merge(sme_ctx *ctx, sme_index *const *indexes, int n, void *stream, sme_index **out);
+/* Of an index sme_index_merge made: its inputs, the terms two or more inputs held,
+ * the postings that merging equal docnos removed (sum of the inputs' P - P), and 1
+ * if the concatenation path ran (disjoint docno ranges, "merge_append").  All four
+ * are 0 for any other index. */
+int sme_index_merge_stats(const sme_index *ix, uint64_t *inputs, uint64_t *shared_terms, uint64_t *merged_postings,
+                          uint64_t *appended);
 
 /* Timing of the last build, per stage, in milliseconds (device events on the
  * build stream), as a JSON object; "tok_kernel" brackets exactly the tokenizer

@@ -60,6 +60,7 @@ EXPORTS = [
     "sme_query_near", "sme_query_near_device", "sme_query_near_stats",
     "sme_query_structured", "sme_query_structured_device", "sme_query_structured_stats",
     "sme_index_feedback_terms", "sme_index_feedback_terms_device", "sme_index_feedback_stats",
+    "sme_index_merge", "sme_index_merge_stats",
 ]
 
 
@@ -174,6 +175,8 @@ def lib():
                                                   C.c_int, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
                                                   C.POINTER(vp), C.POINTER(vp), i64p]
     L.sme_index_feedback_stats.argtypes = [vp] + [C.POINTER(C.c_uint64)] * 5
+    L.sme_index_merge.argtypes = [vp, C.POINTER(vp), C.c_int, vp, C.POINTER(vp)]
+    L.sme_index_merge_stats.argtypes = [vp] + [C.POINTER(C.c_uint64)] * 4
     _lib = L
     return L
 
@@ -355,6 +358,17 @@ class Context:
         arr = (C.c_uint64 * max(n, 1))(*[int(x) for x in sizes])
         h = C.c_void_p()
         _check(lib().sme_merge_pieces(self._h, C.c_void_p(d_blobs), arr, n, None, C.byref(h)))
+        return Index(h, self)
+
+    def merge(self, indexes, stream=None):
+        """sme_index_merge: one full Index from 1..64 indexes of this context (built,
+        loaded or merged, numbered with one docno mapping), taken in list order as
+        the map tasks of one job: what one build of their corpora gives (include/sme.h).
+        The inputs stay valid."""
+        idx = list(indexes)
+        arr = (C.c_void_p * max(len(idx), 1))(*[getattr(i, "_h", None) for i in idx])
+        h = C.c_void_p()
+        _check(lib().sme_index_merge(self._h, arr, len(idx), C.c_void_p(stream or 0), C.byref(h)))
         return Index(h, self)
 
     def build_chargram(self, corpus):
@@ -947,6 +961,13 @@ class Index:
         dn, sc = self.query_topk(expanded, xoff, k)
         return dn, sc, expanded, xoff
 
+    def merge_stats(self):
+        """sme_index_merge_stats: of a merged index its inputs, the terms two or more
+        inputs held, the postings equal docnos merged away and whether the
+        concatenation path ran; zeros for any other index."""
+        i, s, m, a = self._stats(self._h, lib().sme_index_merge_stats, 4)
+        return {"inputs": i, "shared_terms": s, "merged_postings": m, "appended": a}
+
     def reweight(self, n_global, d_df_global=None, stream=None):
         """TF-IDF weights with all-reduced N (and df) of a doc-sharded index."""
         _check(lib().sme_index_reweight(self._h, n_global, C.c_void_p(d_df_global or 0), C.c_void_p(stream or 0)))
@@ -1175,6 +1196,16 @@ class IntDocVectorsForwardIndex:
         ctor, IntDocVectorsForwardIndex.java:93-122)."""
         from . import seqfile
         return cls(seqfile.load_index_dir(ctx, index_dir), mapping)
+
+    def merged(self, other, *more):
+        """A forward index over the merge (Context.merge) of this one's index and the
+        others' -- IntDocVectorsForwardIndex or Index objects of the same context,
+        numbered with the same docno mapping, which the result keeps.  "Add these
+        documents" without rebuilding; this index stays as it is."""
+        idx = [self.index] + [getattr(o, "index", o) for o in (other,) + more]
+        out = IntDocVectorsForwardIndex(self.index.ctx.merge(idx))
+        out._docids = self._docids
+        return out
 
     def getValue(self, terms):  # noqa: N802
         ids = self.index.lookup(list(terms))

@@ -13,6 +13,7 @@
 
 #include "sme_feedback.hpp"
 #include "sme_internal.hpp"
+#include "sme_ixmerge.hpp"
 
 namespace {
 thread_local std::string g_err;
@@ -369,6 +370,15 @@ int sme_set_option(sme_ctx *cx, const char *name, int64_t v) {
                                          std::to_string(sme::feedback::kMinSlots) + ", " +
                                          std::to_string(sme::feedback::kMaxSlots) + "]");
       cx->opt_fb_slots = v;
+    } else if (n == "merge_tile") {
+      if (!sme::ixmerge::legal_tile(v))
+        throw sme::Error(SME_EINVAL, "option " + n + " must be a multiple of 64 in [" +
+                                         std::to_string(sme::ixmerge::kMinTile) + ", " +
+                                         std::to_string(sme::ixmerge::kMaxTile) + "]");
+      cx->opt_merge_tile = v;
+    } else if (n == "merge_append") {
+      range(0, 1);
+      cx->opt_merge_append = v;
     } else {
       throw sme::Error(SME_EINVAL, "unknown option " + n);
     }
@@ -1356,6 +1366,36 @@ int sme_merge_pieces(sme_ctx *cx, const void *d_blobs, const uint64_t *sizes, in
     if (!cx || !d_blobs || !sizes || !out || n < 1) throw sme::Error(SME_EINVAL, "bad argument");
     set_device(cx);
     *out = sme::merge_pieces(cx, (const uint8_t *)d_blobs, sizes, n, stream_of(cx, stream));
+  });
+}
+
+int sme_index_merge(sme_ctx *cx, sme_index *const *indexes, int n, void *stream, sme_index **out) {
+  return guard([&] {
+    if (!cx || !out) throw sme::Error(SME_EINVAL, "null argument");
+    if (!indexes) throw sme::Error(SME_EINVAL, "index merge: a null input list");
+    set_device(cx);
+    hipStream_t st = stream_of(cx, stream);
+    sme_index *ix = nullptr;
+    try {
+      ix = sme::merge_indexes(cx, indexes, n, st);
+    } catch (...) {
+      (void)hipStreamSynchronize(st);  // kernels may still use the scratch that went back to the pool
+      throw;
+    }
+    cx->last_profile = ix->profile;
+    *out = ix;
+  });
+}
+
+int sme_index_merge_stats(const sme_index *ix, uint64_t *inputs, uint64_t *shared_terms, uint64_t *merged_postings,
+                          uint64_t *appended) {
+  return guard([&] {
+    if (!ix || !inputs || !shared_terms || !merged_postings || !appended)
+      throw sme::Error(SME_EINVAL, "null argument");
+    *inputs = ix->mg_inputs;
+    *shared_terms = ix->mg_shared;
+    *merged_postings = ix->mg_merged;
+    *appended = ix->mg_appended;
   });
 }
 

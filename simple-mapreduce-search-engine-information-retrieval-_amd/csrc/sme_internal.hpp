@@ -77,6 +77,8 @@ struct sme_ctx {
   int64_t opt_positions = 0;      // "positions": 1 = a K = 1 build keeps every record's term stream (phrase queries)
   int64_t opt_struct_narrow = 1;  // "struct_narrow": 1 = a structured query's term groups cut its operator leaves' candidates
   int64_t opt_fb_slots = 4096;    // "fb_slots": entries of relevance feedback's on-chip table (16..4096, a power of two)
+  int64_t opt_merge_tile = 1024;  // "merge_tile": postings per tile of the index merger (64..2048, multiples of 64)
+  int64_t opt_merge_append = 1;   // "merge_append": 1 = inputs of disjoint docno ranges are laid end to end, 0 = always merged
   int64_t opt_corpus_keep = int64_t(16) << 30;  // "corpus_keep_bytes": host-corpus builds keep their device copy
                                                 // (no hipMalloc next build) only up to this size
   // pinned host staging of device -> host record copies into pageable caller
@@ -206,6 +208,10 @@ struct sme_index {
   // before the cut, set docnos without a record, sets that took the large path
   sme::TermFreqDocsScores fb;
   uint64_t fb_positions = 0, fb_pairs = 0, fb_kept = 0, fb_missing = 0, fb_spilled = 0;
+  // a merged index (sme_index_merge, sme_ixmerge.hip): its inputs, the terms two or
+  // more of them held, the postings that equal docnos merged away, and whether
+  // the concatenation path ran
+  uint64_t mg_inputs = 0, mg_shared = 0, mg_merged = 0, mg_appended = 0;
   // stage timings of the build that produced this index (ms)
   std::vector<std::pair<std::string, float>> profile;
   ~sme_index() { ctx->live_indexes--; }  // members (pooled buffers) are released after this body
@@ -347,6 +353,9 @@ sme_index *merge_pieces(sme_ctx *cx, const uint8_t *d_blobs, const uint64_t *siz
 // the weights are then written by one flat pass over the postings)
 void reweight_index(sme_index *ix, int64_t N, const int64_t *d_gdf, hipStream_t st,
                     const uint32_t *d_term_of = nullptr);
+// n indexes of cx into one full index (sme_ixmerge.hip): vocabulary union, postings
+// merged by docno with equal docnos summed, both orders, weights, kept streams
+sme_index *merge_indexes(sme_ctx *cx, sme_index *const *ins, int n, hipStream_t st);
 // an index from np partition record streams laid back to back in device memory
 // (sme_load.hip; part_offsets: np + 1 host entries)
 sme_index *load_records(sme_ctx *cx, const uint8_t *d_records, const uint64_t *part_offsets, int np, hipStream_t st);
