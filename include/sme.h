@@ -164,6 +164,9 @@ void sme_destroy(sme_ctx *ctx);
  *   "merge_tile"    sme_index_merge: docno-order postings per tile of its n-way merge, a multiple
  *                   of 64 in 64..2048 (default 1024: 26 KiB of LDS per workgroup).  Results are
  *                   the same
+ *   "delete_tile"   sme_index_delete_docnos: postings per tile of its compaction of the two posting
+ *                   orders, a multiple of 256 in 256..65536 (default 16384; a workgroup takes 12 KiB
+ *                   of LDS whatever the tile).  Results are the same
  *   "merge_append"  sme_index_merge: 1 (default) inputs whose docno ranges are pairwise disjoint
  *                   are laid end to end without merging, 0 every call takes the general merge.
  *                   Results are the same
@@ -451,7 +454,7 @@ int sme_query_boolean_stats(const sme_index *ix, uint64_t *candidates, uint64_t 
  * 0 for an index that keeps none: one built without the option or with K >= 2, a
  * chargram output, and every index from sme_index_from_records* or
  * sme_merge_pieces -- positions cannot be added to an index later; sme_index_merge
- * carries its inputs' over. */
+ * carries its inputs' over, sme_index_delete_docnos those of the surviving records. */
 int sme_index_positions(const sme_index *ix, uint64_t *records, uint64_t *positions, uint64_t *bytes);
 
 /* Phrase queries (no reference counterpart; the reference answers a phrase of m
@@ -880,6 +883,58 @@ int sme_index_merge(sme_ctx *ctx, sme_index *const *indexes, int n, void *stream
  * are 0 for any other index. */
 int sme_index_merge_stats(const sme_index *ix, uint64_t *inputs, uint64_t *shared_terms, uint64_t *merged_postings,
                           uint64_t *appended);
+
+/* Delete documents: a new, full index of ix's context that is, in every array, what
+ * one build gives over ix's records in their order minus every record whose docno
+ * is in the list (n docnos; host memory, or device memory for the _device entry,
+ * which takes for instance the d_docno of sme_query_boolean_device as it is).  ix
+ * is read only and stays valid, and so does its last result of every query
+ * feature.  "Replace document d" is this call followed by sme_index_merge with a
+ * build of the new document.
+ *   the list    any order, duplicates allowed.  Docnos that no record has are
+ *               ignored, values outside the index's docno range, INT32_MIN and
+ *               INT32_MAX included (docno - dmin is taken in 64 bits).  Docno 0
+ *               names every record without a DOCNO, a negative docno the records
+ *               of that unmapped docid.  A docno several records hold (a docid
+ *               occurring twice) removes all of them: the posting that summed
+ *               their tfs goes whole.  n = 0 gives a copy;
+ *   vocabulary  the terms that keep at least one posting, in the same TermDF
+ *               order, ids renumbered densely;
+ *   postings    both orders: ix's list of the term without the removed docnos, in
+ *               ix's order (removing keeps an order, nothing is sorted); offsets
+ *               and df from the surviving counts; P, V follow, N = the surviving
+ *               records, max_tf is recomputed over the survivors (at least 1), and
+ *               the docno range is that of the surviving records;
+ *   weights     those of sme_index_reweight(N) with the new N and df under the
+ *               context's idf mode.  ix's own earlier sme_index_reweight is NOT
+ *               carried over;
+ *   doc counter ix's record list without the removed records.  A surviving record
+ *               starts a map task if and only if no survivor lies between it and
+ *               the nearest task start at or before it: a task that loses its first
+ *               record starts at its next survivor, one that loses every record
+ *               disappears, so the " " record serializes as the reference job over
+ *               the remaining records of those map tasks writes it.  As for a
+ *               merged index, sme_index_record_docnos / sme_index_pack_pieces on
+ *               the result return SME_EINVAL;
+ *   positions   kept if and only if ix keeps them: the surviving records' streams
+ *               in ix's record order, term ids rewritten to the new ids.
+ * The query side and the wildcard table are built on first use, as for any index.
+ * Refused before any per-posting work, with a message: a null ix or out, n < 0,
+ * n > 0 with a null list, a records-only index (sme_merge_pieces output), a
+ * chargram output (all SME_EINVAL); K != 1 is SME_ENOTIMPL ("deleting from K >= 2
+ * indexes").  An index opened from part files (sme_index_from_records*), or merged
+ * from one, is SME_EINVAL too: its doc counter never holds a map task's last
+ * docno, so which record has a docno cannot be decided there.
+ * sme_last_build_profile then holds the stages set, records, postings, terms,
+ * tf_order, weights, positions, total.  stream NULL = the context's stream. */
+int sme_index_delete_docnos(sme_index *ix, const int32_t *docnos, int64_t n, void *stream, sme_index **out);
+int sme_index_delete_docnos_device(sme_index *ix, const int32_t *d_docnos, int64_t n, void *stream,
+                                   sme_index **out);
+/* Of an index sme_index_delete_docnos* made: the distinct listed docnos that at
+ * least one record had, and the records, postings and terms removed.  All four
+ * are 0 for any other index. */
+int sme_index_delete_stats(const sme_index *ix, uint64_t *docnos, uint64_t *records, uint64_t *postings,
+                           uint64_t *terms);
 
 /* Timing of the last build, per stage, in milliseconds (device events on the
  * build stream), as a JSON object; "tok_kernel" brackets exactly the tokenizer

@@ -61,6 +61,7 @@ EXPORTS = [
     "sme_query_structured", "sme_query_structured_device", "sme_query_structured_stats",
     "sme_index_feedback_terms", "sme_index_feedback_terms_device", "sme_index_feedback_stats",
     "sme_index_merge", "sme_index_merge_stats",
+    "sme_index_delete_docnos", "sme_index_delete_docnos_device", "sme_index_delete_stats",
 ]
 
 
@@ -177,6 +178,9 @@ def lib():
     L.sme_index_feedback_stats.argtypes = [vp] + [C.POINTER(C.c_uint64)] * 5
     L.sme_index_merge.argtypes = [vp, C.POINTER(vp), C.c_int, vp, C.POINTER(vp)]
     L.sme_index_merge_stats.argtypes = [vp] + [C.POINTER(C.c_uint64)] * 4
+    L.sme_index_delete_docnos.argtypes = [vp, i32p, C.c_int64, vp, C.POINTER(vp)]
+    L.sme_index_delete_docnos_device.argtypes = [vp, vp, C.c_int64, vp, C.POINTER(vp)]
+    L.sme_index_delete_stats.argtypes = [vp] + [C.POINTER(C.c_uint64)] * 4
     _lib = L
     return L
 
@@ -968,6 +972,33 @@ class Index:
         i, s, m, a = self._stats(self._h, lib().sme_index_merge_stats, 4)
         return {"inputs": i, "shared_terms": s, "merged_postings": m, "appended": a}
 
+    def delete_docnos(self, docnos, stream=None):
+        """sme_index_delete_docnos: a new full Index without the records whose docno
+        is in `docnos` (any order, duplicates and absent docnos allowed) -- in every
+        array what one build of the remaining documents gives (include/sme.h).  This
+        index stays valid."""
+        d = np.ascontiguousarray(np.asarray(docnos, dtype=np.int32).reshape(-1))
+        ptr = d.ctypes.data_as(C.POINTER(C.c_int32)) if d.size else None
+        h = C.c_void_p()
+        _check(lib().sme_index_delete_docnos(self._h, ptr, d.size, C.c_void_p(stream or 0), C.byref(h)))
+        return Index(h, self.ctx)
+
+    def delete_docnos_device(self, d_docnos, n, stream=None):
+        """sme_index_delete_docnos_device: as delete_docnos, the n int32 docnos in device
+        memory at d_docnos -- a device result (query_boolean_device's docnos, say)
+        without a round trip."""
+        h = C.c_void_p()
+        _check(lib().sme_index_delete_docnos_device(self._h, C.c_void_p(d_docnos or 0), int(n), C.c_void_p(stream or 0),
+                                                    C.byref(h)))
+        return Index(h, self.ctx)
+
+    def delete_stats(self):
+        """sme_index_delete_stats: of an index delete_docnos made the distinct listed
+        docnos some record had, and the records, postings and terms removed; zeros
+        for any other index."""
+        d, r, p, t = self._stats(self._h, lib().sme_index_delete_stats, 4)
+        return {"docnos": d, "records": r, "postings": p, "terms": t}
+
     def reweight(self, n_global, d_df_global=None, stream=None):
         """TF-IDF weights with all-reduced N (and df) of a doc-sharded index."""
         _check(lib().sme_index_reweight(self._h, n_global, C.c_void_p(d_df_global or 0), C.c_void_p(stream or 0)))
@@ -1204,6 +1235,32 @@ class IntDocVectorsForwardIndex:
         documents" without rebuilding; this index stays as it is."""
         idx = [self.index] + [getattr(o, "index", o) for o in (other,) + more]
         out = IntDocVectorsForwardIndex(self.index.ctx.merge(idx))
+        out._docids = self._docids
+        return out
+
+    def without(self, docs):
+        """A forward index over this one's index without the given documents
+        (Index.delete_docnos): `docs` holds docnos (ints) and/or docid strings, the
+        strings resolved through the docno mapping this object holds -- an unknown
+        docid, or a docid without a mapping, raises ValueError.  The result keeps the
+        mapping; this index stays as it is.  Replacing a document is a deletion and a
+        merge with a build of its new text:
+
+            fresh = fwd.without(["FT911-3"]).merged(ctx.build(new_text_of_ft911_3))
+        """
+        docnos, by_id = [], None
+        for d in docs:
+            if isinstance(d, str):
+                if self._docids is None:
+                    raise ValueError("docid %r: this forward index holds no docno mapping" % d)
+                if by_id is None:
+                    by_id = {s: i for i, s in enumerate(self._docids) if i > 0}
+                if d not in by_id:
+                    raise ValueError("docid %r is not in the docno mapping" % d)
+                docnos.append(by_id[d])
+            else:
+                docnos.append(int(d))
+        out = IntDocVectorsForwardIndex(self.index.delete_docnos(docnos))
         out._docids = self._docids
         return out
 

@@ -14,6 +14,7 @@
 #include "sme_feedback.hpp"
 #include "sme_internal.hpp"
 #include "sme_ixmerge.hpp"
+#include "sme_ixdelete.hpp"
 
 namespace {
 thread_local std::string g_err;
@@ -376,6 +377,12 @@ int sme_set_option(sme_ctx *cx, const char *name, int64_t v) {
                                          std::to_string(sme::ixmerge::kMinTile) + ", " +
                                          std::to_string(sme::ixmerge::kMaxTile) + "]");
       cx->opt_merge_tile = v;
+    } else if (n == "delete_tile") {
+      if (!sme::ixdelete::legal_tile(v))
+        throw sme::Error(SME_EINVAL, "option " + n + " must be a multiple of 256 in [" +
+                                         std::to_string(sme::ixdelete::kMinTile) + ", " +
+                                         std::to_string(sme::ixdelete::kMaxTile) + "]");
+      cx->opt_delete_tile = v;
     } else if (n == "merge_append") {
       range(0, 1);
       cx->opt_merge_append = v;
@@ -1396,6 +1403,46 @@ int sme_index_merge_stats(const sme_index *ix, uint64_t *inputs, uint64_t *share
     *shared_terms = ix->mg_shared;
     *merged_postings = ix->mg_merged;
     *appended = ix->mg_appended;
+  });
+}
+
+namespace {
+int delete_docnos_entry(sme_index *ix, const int32_t *list, int64_t n, bool on_device, void *stream, sme_index **out) {
+  return guard([&] {
+    hipStream_t st = nullptr;
+    if (ix && out) {  // (a null argument is the validator's to refuse, before anything else)
+      set_device(ix->ctx);
+      st = stream_of(ix->ctx, stream);
+    }
+    sme_index *res = nullptr;
+    try {
+      res = sme::delete_docnos(ix, list, n, on_device, out != nullptr, st);
+    } catch (...) {
+      if (ix && out) (void)hipStreamSynchronize(st);  // kernels may still use the scratch that went back to the pool
+      throw;
+    }
+    ix->ctx->last_profile = res->profile;
+    *out = res;
+  });
+}
+}  // namespace
+
+int sme_index_delete_docnos(sme_index *ix, const int32_t *docnos, int64_t n, void *stream, sme_index **out) {
+  return delete_docnos_entry(ix, docnos, n, false, stream, out);
+}
+
+int sme_index_delete_docnos_device(sme_index *ix, const int32_t *d_docnos, int64_t n, void *stream, sme_index **out) {
+  return delete_docnos_entry(ix, d_docnos, n, true, stream, out);
+}
+
+int sme_index_delete_stats(const sme_index *ix, uint64_t *docnos, uint64_t *records, uint64_t *postings,
+                           uint64_t *terms) {
+  return guard([&] {
+    if (!ix || !docnos || !records || !postings || !terms) throw sme::Error(SME_EINVAL, "null argument");
+    *docnos = ix->dl_docnos;
+    *records = ix->dl_records;
+    *postings = ix->dl_postings;
+    *terms = ix->dl_terms;
   });
 }
 

@@ -79,6 +79,7 @@ struct sme_ctx {
   int64_t opt_fb_slots = 4096;    // "fb_slots": entries of relevance feedback's on-chip table (16..4096, a power of two)
   int64_t opt_merge_tile = 1024;  // "merge_tile": postings per tile of the index merger (64..2048, multiples of 64)
   int64_t opt_merge_append = 1;   // "merge_append": 1 = inputs of disjoint docno ranges are laid end to end, 0 = always merged
+  int64_t opt_delete_tile = 16384; // "delete_tile": postings per tile of the index deletion pass (256..65536, multiples of 256)
   int64_t opt_corpus_keep = int64_t(16) << 30;  // "corpus_keep_bytes": host-corpus builds keep their device copy
                                                 // (no hipMalloc next build) only up to this size
   // pinned host staging of device -> host record copies into pageable caller
@@ -123,6 +124,9 @@ struct sme_index {
   bool records_only = false;  // merged shard pieces (sme_merge_pieces): reduce-order CSR + records, no query side
   // loaded from record streams (sme_index_from_records): d_rec_docno lacks every map task's last docno
   bool from_records = false;
+  // every entry of d_rec_docno is the record's real docno: a build, a merge of such
+  // inputs, a deletion from one -- not an index opened from part files (sme_load.hip)
+  bool rec_complete = true;
   // serialized partitions (lazily built)
   sme::DevBuf d_ser;
   std::vector<int64_t> part_start;  // R+1
@@ -212,6 +216,9 @@ struct sme_index {
   // more of them held, the postings that equal docnos merged away, and whether
   // the concatenation path ran
   uint64_t mg_inputs = 0, mg_shared = 0, mg_merged = 0, mg_appended = 0;
+  // an index sme_index_delete_docnos made (sme_ixdelete.hip): the listed docnos some
+  // record had, and the records, postings and terms that went
+  uint64_t dl_made = 0, dl_docnos = 0, dl_records = 0, dl_postings = 0, dl_terms = 0;
   // stage timings of the build that produced this index (ms)
   std::vector<std::pair<std::string, float>> profile;
   ~sme_index() { ctx->live_indexes--; }  // members (pooled buffers) are released after this body
@@ -356,6 +363,11 @@ void reweight_index(sme_index *ix, int64_t N, const int64_t *d_gdf, hipStream_t 
 // n indexes of cx into one full index (sme_ixmerge.hip): vocabulary union, postings
 // merged by docno with equal docnos summed, both orders, weights, kept streams
 sme_index *merge_indexes(sme_ctx *cx, sme_index *const *ins, int n, hipStream_t st);
+// in without the records whose docno is in the list, as a new full index
+// (sme_ixdelete.hip): both posting orders compacted in place of order, the
+// vocabulary, weights, doc counter and kept streams of the survivors
+sme_index *delete_docnos(sme_index *in, const int32_t *list, int64_t n, bool list_on_device, bool has_out,
+                         hipStream_t st);
 // an index from np partition record streams laid back to back in device memory
 // (sme_load.hip; part_offsets: np + 1 host entries)
 sme_index *load_records(sme_ctx *cx, const uint8_t *d_records, const uint64_t *part_offsets, int np, hipStream_t st);

@@ -618,6 +618,8 @@ sme_index *merge_indexes(sme_ctx *cx, sme_index *const *ins, int n, hipStream_t 
       any_rec = true;
     }
   }
+  bool rec_complete = true;  // every input with records holds every record's real docno
+  for (int a = 0; a < n; a++) rec_complete &= ins[a]->N == 0 || ins[a]->rec_complete;
   if (!any_ps) keep_ps = false;
   const int64_t Vt = tbase[(size_t)n];
   if (Pt > 0xFFFFFFFFll) throw Error(SME_ELIMIT, "index merge: more than 2^32 postings");
@@ -662,6 +664,7 @@ sme_index *merge_indexes(sme_ctx *cx, sme_index *const *ins, int n, hipStream_t 
   ix->idf_mode = cx->cfg.idf_mode;
   ix->from_records = true;  // the doc counter is kept as its postings: no record docnos, no pieces
   ix->N = N;
+  ix->rec_complete = rec_complete;
   if (any_rec) {
     ix->dmin = dmin;
     ix->dmax = dmax;

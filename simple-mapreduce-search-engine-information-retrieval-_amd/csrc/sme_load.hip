@@ -550,6 +550,7 @@ sme_index *load_records(sme_ctx *cx, const uint8_t *s, const uint64_t *part_offs
   ix->R = cx->cfg.num_partitions;
   ix->idf_mode = cx->cfg.idf_mode;
   ix->from_records = true;
+  ix->rec_complete = false;  // k_load_counter stores 0 for every map task's last docno
 
   uint64_t *po = W[0].as<uint64_t>((size_t)np + 2);
   SME_HIP(hipMemcpyAsync(po, hpo.data(), ((size_t)np + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
