@@ -453,7 +453,8 @@ int sme_query_boolean_stats(const sme_index *ix, uint64_t *candidates, uint64_t 
  * = term positions over all of them, *bytes = device memory they take; all three
  * 0 for an index that keeps none: one built without the option or with K >= 2, a
  * chargram output, and every index from sme_index_from_records* or
- * sme_merge_pieces -- positions cannot be added to an index later; sme_index_merge
+ * sme_merge_pieces.  A K = 1 index with a query side that keeps none gets them
+ * from a positions file (sme_index_attach_positions, below); sme_index_merge
  * carries its inputs' over, sme_index_delete_docnos those of the surviving records. */
 int sme_index_positions(const sme_index *ix, uint64_t *records, uint64_t *positions, uint64_t *bytes);
 
@@ -935,6 +936,83 @@ int sme_index_delete_docnos_device(sme_index *ix, const int32_t *d_docnos, int64
  * are 0 for any other index. */
 int sme_index_delete_stats(const sme_index *ix, uint64_t *docnos, uint64_t *records, uint64_t *postings,
                            uint64_t *terms);
+
+/* The positions file: the term streams (sme_index_positions) of an index in a file
+ * form, written on the device from any index that keeps positions and attached on
+ * the device to one that keeps none -- an index opened from its part files
+ * (sme_index_from_records*) answers phrase, proximity, structured and feedback calls
+ * again without the corpus.  The format is this library's own (no reference
+ * counterpart); all integers are little-endian:
+ *   offset 0   8 magic bytes 53 4D 45 50 4F 53 00 01 ("SMEPOS", 0, 1)
+ *          8   u32 version = 1
+ *         12   u32 bits b, need <= b <= 31, need = max(1, bit length of (V - 1))
+ *         16   u64 records Rn (= the index's N, < 2^31)
+ *         24   u64 positions T (< 2^31, the build's own limit)
+ *         32   u64 V
+ *         40   u64 vocabulary digest
+ *         48   16 reserved bytes, zero
+ *         64   int32 docno[Rn], ascending in signed order (equal values allowed),
+ *              zero-padded to a multiple of 8 bytes
+ *         then u32 len[Rn], padded likewise; their sum is T
+ *         then u64 word[ceil(T b / 64)]: position p's id occupies bits [p b, (p + 1) b)
+ *              of the words seen as one little-endian bit string (bit i = bit i mod 64
+ *              of word i / 64); the unused high bits of the last word are zero.
+ * The file ends exactly there.  Records are in the order of the streams: docno
+ * ascending, records of equal docno in the order the index holds them.
+ * digest = sum over t < V of h_t mod 2^64, h_t = FNV-1a-64 (offset basis
+ * 0xcbf29ce484222325, prime 0x100000001b3) over the 8 bytes of t, little-endian,
+ * followed by term t's UTF-16 code units, each low byte first.
+ *
+ * Writing.  bits = 0 writes the narrowest width, need; any b in [need, 31] is a
+ * valid file; another value is SME_EINVAL.  *buf / *d_buf (n bytes; host memory from
+ * the host entry, which is the device entry plus one copy; device memory from the
+ * device entry) are owned by the index until its next posfile call and leave every
+ * other feature's result buffers alone.  SME_EINVAL, with a message that says which:
+ * an index without positions, one with K != 1, one without a query side, a chargram
+ * output.  sme_last_build_profile then holds the stages digest, sections, encode,
+ * total.
+ *
+ * Attaching fills the streams of an existing K = 1 TermKGramDocIndexer index that
+ * has a query side and keeps no positions (loaded, built without the option, merged
+ * or deleted without them) in place; d_file is 8-byte aligned.  flags: 0, or
+ * SME_ATTACH_NO_CROSSCHECK.  SME_EINVAL, with a message that says which: an index
+ * that already keeps positions, K != 1, a chargram output, a records-only index,
+ * unknown flag bits.  Nothing in the file is trusted, and a refused file leaves the
+ * index exactly as it was.  Checked, in this order:
+ *   header      on the host (the device entry copies 64 bytes down first): magic,
+ *               version, reserved bytes, bits, records == N, V == the index's V, the
+ *               limits, and the exact file size, computed with overflow-checked
+ *               arithmetic before any section offset is used.  SME_EPARSE with a
+ *               message naming the field; positions >= 2^31 is SME_ELIMIT;
+ *   digest      computed on the device over the index's term strings; a mismatch is
+ *               SME_EPARSE, "written for another vocabulary";
+ *   structure   on the device while decoding: docnos ascending, the lengths adding up
+ *               to positions, every id < V, zero padding.  SME_EPARSE, the message
+ *               naming the first offending record or position.  These checks keep
+ *               every later kernel that indexes by a stream id in bounds and always run;
+ *   cross-check (unless SME_ATTACH_NO_CROSSCHECK) every posting (t, d, tf) of the index
+ *               has exactly tf positions holding t in the records of docno d, and
+ *               every position's (id, docno) has a posting.  SME_EPARSE, the message
+ *               naming the first (term id, then docno) that disagrees.  An index's own
+ *               file passes.  Without it a file with the right structure and the
+ *               wrong content is accepted: the flag is for files one wrote oneself.
+ * Afterwards sme_index_positions reports the streams, and sme_query_phrase / _near /
+ * _structured, sme_index_feedback_terms and sme_index_merge treat the index as a
+ * built one.  sme_index_delete_docnos still refuses an index opened from part files.
+ * sme_last_build_profile then holds the stages header, digest, records, decode,
+ * crosscheck, total.  stream NULL = the context's stream.
+ *
+ * sme_index_posfile_stats reports on the last posfile call on the index: the file's
+ * bytes and width, the postings the cross-check compared (P; 0 without it, and after
+ * a write), and the device times of the encode kernel (a write), the decode kernel
+ * and the cross-check (an attach); the time pointers may be NULL. */
+#define SME_ATTACH_NO_CROSSCHECK 1
+int sme_index_positions_file(sme_index *ix, int bits, void *stream, const uint8_t **buf, size_t *n);
+int sme_index_positions_file_device(sme_index *ix, int bits, void *stream, const void **d_buf, size_t *n);
+int sme_index_attach_positions(sme_index *ix, const uint8_t *file, size_t n, int flags, void *stream);
+int sme_index_attach_positions_device(sme_index *ix, const void *d_file, size_t n, int flags, void *stream);
+int sme_index_posfile_stats(const sme_index *ix, uint64_t *file_bytes, uint64_t *bits, uint64_t *checked_postings,
+                            float *encode_ms, float *decode_ms, float *crosscheck_ms);
 
 /* Timing of the last build, per stage, in milliseconds (device events on the
  * build stream), as a JSON object; "tok_kernel" brackets exactly the tokenizer

@@ -62,6 +62,8 @@ EXPORTS = [
     "sme_index_feedback_terms", "sme_index_feedback_terms_device", "sme_index_feedback_stats",
     "sme_index_merge", "sme_index_merge_stats",
     "sme_index_delete_docnos", "sme_index_delete_docnos_device", "sme_index_delete_stats",
+    "sme_index_positions_file", "sme_index_positions_file_device", "sme_index_attach_positions",
+    "sme_index_attach_positions_device", "sme_index_posfile_stats",
 ]
 
 
@@ -181,6 +183,11 @@ def lib():
     L.sme_index_delete_docnos.argtypes = [vp, i32p, C.c_int64, vp, C.POINTER(vp)]
     L.sme_index_delete_docnos_device.argtypes = [vp, vp, C.c_int64, vp, C.POINTER(vp)]
     L.sme_index_delete_stats.argtypes = [vp] + [C.POINTER(C.c_uint64)] * 4
+    L.sme_index_positions_file.argtypes = [vp, C.c_int, vp, C.POINTER(vp), C.POINTER(sz)]
+    L.sme_index_positions_file_device.argtypes = [vp, C.c_int, vp, C.POINTER(vp), C.POINTER(sz)]
+    L.sme_index_attach_positions.argtypes = [vp, vp, sz, C.c_int, vp]
+    L.sme_index_attach_positions_device.argtypes = [vp, vp, sz, C.c_int, vp]
+    L.sme_index_posfile_stats.argtypes = [vp] + [C.POINTER(C.c_uint64)] * 3 + [C.POINTER(C.c_float)] * 3
     _lib = L
     return L
 
@@ -999,6 +1006,57 @@ class Index:
         d, r, p, t = self._stats(self._h, lib().sme_index_delete_stats, 4)
         return {"docnos": d, "records": r, "postings": p, "terms": t}
 
+    ATTACH_NO_CROSSCHECK = 1  # SME_ATTACH_NO_CROSSCHECK
+
+    def positions_file(self, bits=0, stream=None):
+        """sme_index_positions_file: the term streams this index keeps (positions) as
+        the bytes of a positions file (include/sme.h has the format), written on the
+        device; bits 0 = the narrowest id width, else a width up to 31.  Another
+        index of the same documents and vocabulary -- one opened from its part
+        files, say -- takes them back with attach_positions."""
+        p, n = C.c_void_p(), C.c_size_t()
+        _check(lib().sme_index_positions_file(self._h, int(bits), C.c_void_p(stream or 0), C.byref(p), C.byref(n)))
+        return _host_bytes(p.value, n.value)
+
+    def positions_file_device(self, bits=0, stream=None):
+        """sme_index_positions_file_device: (device pointer, byte count) of the same
+        file, left in HBM; it belongs to the index until its next posfile call."""
+        p, n = C.c_void_p(), C.c_size_t()
+        _check(lib().sme_index_positions_file_device(self._h, int(bits), C.c_void_p(stream or 0), C.byref(p),
+                                                     C.byref(n)))
+        return p.value, n.value
+
+    def attach_positions(self, data, crosscheck=True, stream=None):
+        """sme_index_attach_positions: give this K = 1 index, which keeps no positions,
+        the term streams of a positions file (bytes-like).  The file is checked against
+        its header, this index's vocabulary and, with crosscheck, every posting's tf; a
+        refused file (SmeError, code -4) leaves the index as it was.  Afterwards phrase,
+        proximity, structured and feedback calls and merges treat it as built with
+        positions."""
+        buf = np.frombuffer(data, dtype=np.uint8) if len(data) else np.zeros(0, np.uint8)
+        keep = np.ascontiguousarray(buf) if buf.size else np.zeros(1, np.uint8)
+        _check(lib().sme_index_attach_positions(self._h, C.c_void_p(keep.ctypes.data), buf.size,
+                                                0 if crosscheck else Index.ATTACH_NO_CROSSCHECK,
+                                                C.c_void_p(stream or 0)))
+
+    def attach_positions_device(self, d_file, nbytes, crosscheck=True, stream=None):
+        """sme_index_attach_positions_device: as attach_positions, the file's nbytes in
+        device memory at d_file (8-byte aligned)."""
+        _check(lib().sme_index_attach_positions_device(self._h, C.c_void_p(d_file or 0), int(nbytes),
+                                                       0 if crosscheck else Index.ATTACH_NO_CROSSCHECK,
+                                                       C.c_void_p(stream or 0)))
+
+    def posfile_stats(self):
+        """sme_index_posfile_stats: of the last positions_file / attach_positions call
+        on this index the file's bytes and id width, the postings the cross-check
+        compared, and the device times of the encode kernel, the decode kernel and the
+        cross-check (ms; zero for what the call did not run)."""
+        u = [C.c_uint64() for _ in range(3)]
+        f = [C.c_float() for _ in range(3)]
+        _check(lib().sme_index_posfile_stats(self._h, *[C.byref(x) for x in u + f]))
+        return {"file_bytes": u[0].value, "bits": u[1].value, "checked_postings": u[2].value,
+                "encode_ms": f[0].value, "decode_ms": f[1].value, "crosscheck_ms": f[2].value}
+
     def reweight(self, n_global, d_df_global=None, stream=None):
         """TF-IDF weights with all-reduced N (and df) of a doc-sharded index."""
         _check(lib().sme_index_reweight(self._h, n_global, C.c_void_p(d_df_global or 0), C.c_void_p(stream or 0)))
@@ -1220,13 +1278,18 @@ class IntDocVectorsForwardIndex:
             self._docids = ids
 
     @classmethod
-    def from_dir(cls, ctx, index_dir, mapping=None):
+    def from_dir(cls, ctx, index_dir, mapping=None, positions=False):
         """The reference's second program: open a reduce output directory
         (part-00000 ...) written earlier -- by TermKGramDocIndexer.run here or by
         the Hadoop job -- and answer queries from it (IntDocVectorsForwardIndex
-        ctor, IntDocVectorsForwardIndex.java:93-122)."""
+        ctor, IntDocVectorsForwardIndex.java:93-122).  positions: also attach the
+        term streams of the directory's positions file (seqfile.write_positions),
+        so phrase and proximity queries work; FileNotFoundError if it is missing."""
         from . import seqfile
-        return cls(seqfile.load_index_dir(ctx, index_dir), mapping)
+        ix = seqfile.load_index_dir(ctx, index_dir)
+        if positions:
+            seqfile.attach_positions(ix, index_dir)
+        return cls(ix, mapping)
 
     def merged(self, other, *more):
         """A forward index over the merge (Context.merge) of this one's index and the

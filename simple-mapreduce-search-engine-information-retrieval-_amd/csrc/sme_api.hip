@@ -1446,6 +1446,77 @@ int sme_index_delete_stats(const sme_index *ix, uint64_t *docnos, uint64_t *reco
   });
 }
 
+int sme_index_positions_file_device(sme_index *ix, int bits, void *stream, const void **d_buf, size_t *n) {
+  return guard([&] {
+    sme::check_positions_file_call(ix, d_buf && n, bits);
+    set_device(ix->ctx);
+    hipStream_t st = stream_of(ix->ctx, stream);
+    try {
+      sme::positions_file(ix, bits, st);
+    } catch (...) {
+      (void)hipStreamSynchronize(st);  // kernels may still use the scratch that went back to the pool
+      throw;
+    }
+    *d_buf = ix->d_pf_file.p;
+    *n = (size_t)ix->pf_bytes;
+  });
+}
+
+int sme_index_positions_file(sme_index *ix, int bits, void *stream, const uint8_t **buf, size_t *n) {
+  return guard([&] {
+    sme::check_positions_file_call(ix, buf && n, bits);
+    const void *d = nullptr;
+    size_t bytes = 0;
+    const int rc = sme_index_positions_file_device(ix, bits, stream, &d, &bytes);
+    if (rc != SME_OK) throw sme::Error(rc, g_err);
+    ix->h_pf_file.resize(std::max<size_t>(bytes, 1));
+    hipStream_t st = stream_of(ix->ctx, stream);
+    SME_HIP(hipMemcpyAsync(ix->h_pf_file.data(), d, bytes, hipMemcpyDeviceToHost, st));
+    SME_HIP(hipStreamSynchronize(st));
+    *buf = ix->h_pf_file.data();
+    *n = bytes;
+  });
+}
+
+namespace {
+int attach_positions_entry(sme_index *ix, const uint8_t *h_file, const void *d_file, size_t n, int flags, void *stream) {
+  return guard([&] {
+    hipStream_t st = nullptr;
+    if (ix) {  // (a null argument is the validator's to refuse, before anything else)
+      set_device(ix->ctx);
+      st = stream_of(ix->ctx, stream);
+    }
+    try {
+      sme::attach_positions(ix, h_file, d_file, n, flags, true, st);
+    } catch (...) {
+      if (ix) (void)hipStreamSynchronize(st);  // kernels may still use the scratch that went back to the pool
+      throw;
+    }
+  });
+}
+}  // namespace
+
+int sme_index_attach_positions(sme_index *ix, const uint8_t *file, size_t n, int flags, void *stream) {
+  return attach_positions_entry(ix, file, nullptr, n, flags, stream);
+}
+
+int sme_index_attach_positions_device(sme_index *ix, const void *d_file, size_t n, int flags, void *stream) {
+  return attach_positions_entry(ix, nullptr, d_file, n, flags, stream);
+}
+
+int sme_index_posfile_stats(const sme_index *ix, uint64_t *file_bytes, uint64_t *bits, uint64_t *checked_postings,
+                            float *encode_ms, float *decode_ms, float *crosscheck_ms) {
+  return guard([&] {
+    if (!ix || !file_bytes || !bits || !checked_postings) throw sme::Error(SME_EINVAL, "null argument");
+    *file_bytes = ix->pf_bytes;
+    *bits = ix->pf_bits;
+    *checked_postings = ix->pf_checked;
+    if (encode_ms) *encode_ms = ix->pf_encode_ms;
+    if (decode_ms) *decode_ms = ix->pf_decode_ms;
+    if (crosscheck_ms) *crosscheck_ms = ix->pf_crosscheck_ms;
+  });
+}
+
 int sme_last_build_profile(const sme_ctx *cx, const char **json) {
   return guard([&] {
     if (!cx || !json) throw sme::Error(SME_EINVAL, "null argument");

@@ -219,6 +219,12 @@ struct sme_index {
   // an index sme_index_delete_docnos made (sme_ixdelete.hip): the listed docnos some
   // record had, and the records, postings and terms that went
   uint64_t dl_made = 0, dl_docnos = 0, dl_records = 0, dl_postings = 0, dl_terms = 0;
+  // the positions file (sme_posfile.hip): the last file written (device bytes, and the
+  // host copy the host entry hands out), and the last posfile call's counts and times
+  sme::DevBuf d_pf_file;
+  std::vector<uint8_t> h_pf_file;
+  uint64_t pf_bytes = 0, pf_bits = 0, pf_checked = 0;
+  float pf_encode_ms = 0.0f, pf_decode_ms = 0.0f, pf_crosscheck_ms = 0.0f;
   // stage timings of the build that produced this index (ms)
   std::vector<std::pair<std::string, float>> profile;
   ~sme_index() { ctx->live_indexes--; }  // members (pooled buffers) are released after this body
@@ -227,7 +233,7 @@ struct sme_index {
     for (sme::DevBuf *b : {&d_term_off, &d_term_chars, &d_off, &d_docno_d, &d_tf_d, &d_w, &d_idf, &d_lut, &d_gram, &d_docno_o,
                            &d_tf_o, &d_rec_docno, &d_rec_first, &d_ser, &d_hrow_of, &d_heavy, &d_spk, &d_wkeys, &d_wgoff,
                            &d_wgterm, &d_wx_in, &d_wx_plan, &d_wx_choff, &d_wx_moff, &d_wx_scan, &d_ps_off, &d_ps_terms,
-                           &d_ps_docno, &d_nq_lut})
+                           &d_ps_docno, &d_nq_lut, &d_pf_file})
       b->pool = &c->pool;
     for (sme::ResultSet *r : std::initializer_list<sme::ResultSet *>{&wx, &fz, &bq, &pq, &nq, &sq, &sv, &fb})
       r->bind(&c->pool);
@@ -368,6 +374,15 @@ sme_index *merge_indexes(sme_ctx *cx, sme_index *const *ins, int n, hipStream_t 
 // vocabulary, weights, doc counter and kept streams of the survivors
 sme_index *delete_docnos(sme_index *in, const int32_t *list, int64_t n, bool list_on_device, bool has_out,
                          hipStream_t st);
+// the term streams as a file (sme_posfile.hip): written into ix->d_pf_file from an
+// index that keeps positions (bits 0: the narrowest width), and attached -- decoded,
+// checked against the header, the vocabulary and, unless flags says not to, the
+// postings -- to one that keeps none, from host (h_file) or device (d_file) bytes.
+// The two validators of a call throw SME_EINVAL before anything else happens.
+void check_positions_file_call(const sme_index *ix, bool has_args, int bits);
+void positions_file(sme_index *ix, int bits, hipStream_t st);
+void attach_positions(sme_index *ix, const uint8_t *h_file, const void *d_file, size_t n, int flags, bool has_args,
+                      hipStream_t st);
 // an index from np partition record streams laid back to back in device memory
 // (sme_load.hip; part_offsets: np + 1 host entries)
 sme_index *load_records(sme_ctx *cx, const uint8_t *d_records, const uint64_t *part_offsets, int np, hipStream_t st);

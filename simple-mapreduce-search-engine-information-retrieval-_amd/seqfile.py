@@ -17,6 +17,9 @@ sme_index_partition_records).  This module is the host-side step after it:
   read_part_body /       SequenceFile.Reader.init [Hadoop 0.20]: the header checked field by
   load_index_dir         field; what follows it (records and sync escapes) goes to the device
                          loader as it is (sme_index_from_records).
+  write_positions /      the term streams of an index with positions as the directory's
+  attach_positions       _positions file, and back onto the index load_index_dir opened
+                         (sme_index_positions_file / sme_index_attach_positions).
   ForwardIndex           IntDocVectorsForwardIndex ctor + getValue(String)
                          (IntDocVectorsForwardIndex.java:93-122,148-184): term -> (file, pos)
                          -> one record read after seek.
@@ -135,6 +138,29 @@ def load_index_dir(ctx, index_dir):
         with open(path, "rb") as f:
             parts.append(read_part_body(f.read())[0])
     return ctx.load_records(parts)
+
+
+POSITIONS_FILE = "_positions"  # the leading underscore keeps it out of what Hadoop and load_index_dir take for parts
+
+
+def write_positions(ix, out_dir, bits=0):
+    """The term streams of an index that keeps positions as out_dir/_positions
+    (Index.positions_file; include/sme.h has the format), beside the part files
+    write_index_dir writes.  Returns the path."""
+    os.makedirs(out_dir, exist_ok=True)
+    path = os.path.join(out_dir, POSITIONS_FILE)
+    with open(path, "wb") as f:
+        f.write(ix.positions_file(bits))
+    return path
+
+
+def attach_positions(ix, index_dir, crosscheck=True):
+    """Attach index_dir/_positions to an index opened from that directory
+    (Index.attach_positions); FileNotFoundError if the directory has none."""
+    with open(os.path.join(index_dir, POSITIONS_FILE), "rb") as f:
+        data = f.read()
+    ix.attach_positions(data, crosscheck)
+    return ix
 
 
 def key_grams(key):
