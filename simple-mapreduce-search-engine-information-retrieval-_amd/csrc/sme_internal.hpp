@@ -362,6 +362,49 @@ void serialize_index(sme_index *ix, hipStream_t st);
 // shard's terms and postings, and the owner's merge of the received blobs
 void pack_pieces(sme_index *ix, int world, uint8_t *d_out, uint64_t *sizes, hipStream_t st);
 sme_index *merge_pieces(sme_ctx *cx, const uint8_t *d_blobs, const uint64_t *sizes, int np, hipStream_t st);
+// the vocabulary union of n sources (sme_vunion.hip; merge_pieces and merge_indexes
+// stand on it).  Every source term is ranked among the other sources' sorted term
+// lists by String.compareTo: equal strings are adjacent in rank order, sources in
+// the order ord gives them.  A rank position is a SEGMENT, one source's posting list
+// of one term; a scan of the first-occurrence flags numbers the merged terms, whose
+// strings come from their first source.  Writes V, Vt, d_term_off and d_term_chars
+// of ix (V == 0: one zero offset).  d_tbase: n + 1 term bases, Vt = d_tbase[n] < 2^31;
+// d_shared: a zeroed counter of the terms two or more sources hold, or null.  The
+// caller owns the scratch; st is synchronised on return.
+struct TermSource {  // device pointers of one source
+  const int64_t *toff;
+  const uint16_t *tch;
+  int64_t n;  // terms
+  const int64_t *off;
+  const int32_t *dn, *tf;  // its postings, by term
+};
+struct UnionScratch {
+  DevBuf &pos, &at_pos, &first_at, &cnt_at, &pstart, &excl, &seg_key, &seg_val, &gid, &tmap, &gstart, &glen, &scan;
+};
+struct VocabUnion {
+  int64_t V;                        // merged terms
+  const int64_t *pos;               // [Vt] rank position of flat source term j
+  const int64_t *at_pos;            // [Vt] its inverse
+  const uint8_t *first_at;          // [Vt] the segment is its term's first
+  const int32_t *gid;               // [Vt] merged term of a segment
+  const int64_t *gstart;            // [V + 1] first segment of a merged term
+  const int32_t *tmap;              // [Vt] merged term of flat source term j
+  const int64_t *pstart;            // [Vt + 1] the segments' lists laid end to end
+  const int32_t *const *seg_key;    // [Vt] a segment's docnos
+  const int32_t *const *seg_val;    // [Vt] and tfs
+};
+VocabUnion union_vocab(const TermSource *d_src, int n, const int64_t *d_tbase, const int32_t *d_ord, int64_t Vt,
+                       sme_index *ix, unsigned long long *d_shared, UnionScratch s, hipStream_t st);
+// off[g] = pstart[gstart[g]], g < V: the term offsets when the segments laid end to
+// end are the postings
+void segment_term_offsets(const int64_t *pstart, const int64_t *gstart, int64_t V, int64_t *off, hipStream_t st);
+// the reducer's final order (sme_vunion.hip): P postings (dn, tf) grouped by term,
+// term[i] < V their term ids, stably sorted by (term, tf desc) into (odn, otf) --
+// keys term << tfb | (max_tf - tf) of the items in perm order (null: as they lie)
+// through kv_sort<uint64_t>, then a gather.  The caller owns the scratch.
+void sort_term_tf(const uint32_t *term, const int32_t *dn, const int32_t *tf, const uint32_t *perm, int64_t P,
+                  int64_t V, int max_tf, int32_t *odn, int32_t *otf, DevBuf &q0, DevBuf &q1, DevBuf &v0, DevBuf &v1,
+                  DevBuf &radix, hipStream_t st);
 // (d_term_of: the term id of every docno-order posting, if the caller has it --
 // the weights are then written by one flat pass over the postings)
 void reweight_index(sme_index *ix, int64_t N, const int64_t *d_gdf, hipStream_t st,

@@ -32,6 +32,7 @@
 
 #include "sme_internal.hpp"
 #include "sme_ixdelete.hpp"
+#include "sme_ixparts.hpp"
 
 namespace sme {
 
@@ -43,29 +44,6 @@ constexpr int kNT = 256;
 constexpr int kPer = 4;              // postings per lane and step: one 16-byte load
 constexpr int kStep = kNT * kPer;    // postings per workgroup step, and the LDS staging rows
 constexpr int kWaves = kNT / 64;
-
-unsigned grid_n(int64_t n, int nt = kNT, int64_t cap = 16384) {
-  return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + nt - 1) / nt, cap));
-}
-template <typename T>
-T rd1(const T *d, hipStream_t st) {
-  T h;
-  SME_HIP(hipMemcpyAsync(&h, d, sizeof(T), hipMemcpyDeviceToHost, st));
-  SME_HIP(hipStreamSynchronize(st));
-  return h;
-}
-
-// last index r in [lo, hi) with tab[r] <= p (tab ascending, tab[lo] <= p)
-__device__ __forceinline__ int64_t last_le(const int64_t *tab, int64_t lo, int64_t hi, int64_t p) {
-  for (int it = 0; it < 64 && hi - lo > 1; it++) {
-    const int64_t m = lo + ((hi - lo) >> 1);
-    if (tab[m] <= p)
-      lo = m;
-    else
-      hi = m;
-  }
-  return lo;
-}
 
 struct Bits {  // the docno bitmap
   uint32_t *bm;
@@ -299,28 +277,18 @@ template <typename E, bool REMAP>
 __global__ __launch_bounds__(kNT) void k_gather(const int64_t *ooff, int64_t nrow, const int32_t *src,
                                                 const int64_t *ioff, const E *in, int64_t M, const int32_t *tmap,
                                                 int64_t V, E *out, int *err) {
-  __shared__ int64_t s_r[2];
-  const int64_t nblk = (M + 1023) / 1024;
-  for (int64_t b = blockIdx.x; b < nblk; b += gridDim.x) {
-    const int64_t p0 = b * 1024, p1 = min(M, p0 + 1024);
-    if (threadIdx.x < 2) s_r[threadIdx.x] = last_le(ooff, 0, nrow + 1, threadIdx.x ? p1 - 1 : p0);
-    __syncthreads();
-    const int64_t w0 = s_r[0], w1 = s_r[1] + 1;
-    for (int64_t p = p0 + threadIdx.x; p < p1; p += kNT) {
-      const int64_t o = last_le(ooff, w0, w1, p);
-      E v = in[ioff[src[o]] + (p - ooff[o])];
-      if (REMAP && (int64_t)v >= 0) {
-        const int32_t g = (int64_t)v < V ? tmap[(int64_t)v] : -1;
-        if (g < 0) {
-          atomicExch(err, 1);
-          continue;
-        }
-        v = (E)g;
+  for_row_elements<kNT>(ooff, nrow, M, [&](int64_t p, int64_t o) {
+    E v = in[ioff[src[o]] + (p - ooff[o])];
+    if (REMAP && (int64_t)v >= 0) {
+      const int32_t g = (int64_t)v < V ? tmap[(int64_t)v] : -1;
+      if (g < 0) {
+        atomicExch(err, 1);
+        return;
       }
-      out[p] = v;
+      v = (E)g;
     }
-    __syncthreads();
-  }
+    out[p] = v;
+  });
 }
 
 // ---- positions ------------------------------------------------------------------------------

@@ -1,8 +1,8 @@
 // sme_ixmerge.hip -- several indexes of one context into one full index
 // (sme_index_merge; include/sme.h has the semantics, DESIGN.md 4k the pass).
 //
-//   terms      every input term ranked among the other inputs' sorted term lists
-//              (String.compareTo; the scheme of sme_merge.hip's k_merge_rank):
+//   terms      union_vocab (sme_vunion.hip, shared with sme_merge.hip): every input
+//              term ranked among the other inputs' sorted term lists (String.compareTo);
 //              equal strings are adjacent in rank order, sources in order.  A rank
 //              position is a SEGMENT -- one input's posting list of one term -- and
 //              the segments of a merged term are consecutive.  The per-input table
@@ -18,7 +18,7 @@
 //              tiles' output sizes, one scan their places, an emit pass writes --
 //              no temporary of the postings' size, and short terms share a tile.
 //              Disjoint docno ranges: no merge, one flat copy (segments in range order).
-//   tf order   tf_sort_segments, or a stable kv_sort past kTfSortMaxTf
+//   tf order   tf_sort_segments, or sort_term_tf (a stable kv_sort) past kTfSortMaxTf
 //   weights    reweight_index with N = sum N_i, one flat pass (term id per posting)
 //   positions  the same tiled merge over the inputs' record docnos (exact cuts, no
 //              summing), a scan of the record lengths, one flat gather of the streams
@@ -30,6 +30,7 @@
 
 #include "sme_internal.hpp"
 #include "sme_ixmerge.hpp"
+#include "sme_ixparts.hpp"
 
 namespace sme {
 
@@ -38,14 +39,6 @@ namespace {
 using namespace ixmerge;
 
 constexpr int kNT = 256;
-
-struct InDev {  // one input (device pointers)
-  const int64_t *toff;
-  const uint16_t *tch;
-  int64_t n;  // terms
-  const int64_t *off;
-  const int32_t *dn, *tf;  // docno-order postings
-};
 
 // the segments of a merge: ascending lists, grouped by merged term, the sources
 // of a term in order
@@ -57,141 +50,6 @@ struct Segs {
   const int64_t *gstart;      // [G + 1] first segment of a merged term
   int64_t nseg, G, total;
 };
-
-unsigned grid_n(int64_t n, int nt = kNT, int64_t cap = 16384) {
-  return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + nt - 1) / nt, cap));
-}
-int bits_of(uint64_t v) {
-  int b = 1;
-  while (b < 64 && (1ull << b) <= v) b++;
-  return b;
-}
-template <typename T>
-T rd1(const T *d, hipStream_t st) {
-  T h;
-  SME_HIP(hipMemcpyAsync(&h, d, sizeof(T), hipMemcpyDeviceToHost, st));
-  SME_HIP(hipStreamSynchronize(st));
-  return h;
-}
-
-// String.compareTo of units a[0, la) and b[0, lb)
-__device__ __forceinline__ int cmp_units(const uint16_t *a, int64_t la, const uint16_t *b, int64_t lb) {
-  const int64_t m = la < lb ? la : lb;
-  for (int64_t i = 0; i < m; i++)
-    if (a[i] != b[i]) return (int)a[i] - (int)b[i];
-  return la < lb ? -1 : (la > lb ? 1 : 0);
-}
-// first term of input p that is >= s (upper: > s); the interval halves every step
-__device__ int64_t term_bound(const InDev &p, const uint16_t *s, int64_t ls, bool upper) {
-  int64_t lo = 0, hi = p.n;
-  for (int it = 0; it < 64 && lo < hi; it++) {
-    const int64_t m = lo + ((hi - lo) >> 1);
-    const int c = cmp_units(p.tch + p.toff[m], p.toff[m + 1] - p.toff[m], s, ls);
-    if (c < 0 || (upper && c == 0))
-      lo = m + 1;
-    else
-      hi = m;
-  }
-  return lo;
-}
-__device__ __forceinline__ int input_of(const int64_t *base, int n, int64_t j) {
-  int a = 0;
-  while (a + 1 < n && base[a + 1] <= j) a++;
-  return a;
-}
-// last index r in [lo, hi) with tab[r] <= p (tab ascending, tab[lo] <= p)
-__device__ __forceinline__ int64_t last_le(const int64_t *tab, int64_t lo, int64_t hi, int64_t p) {
-  for (int it = 0; it < 64 && hi - lo > 1; it++) {
-    const int64_t m = lo + ((hi - lo) >> 1);
-    if (tab[m] <= p)
-      lo = m;
-    else
-      hi = m;
-  }
-  return lo;
-}
-
-// rank of every input term in the merged sequence: equal strings adjacent, in
-// source order (ord[a]: input a's place in it); first: no earlier source holds it
-__global__ void k_rank(const InDev *in, int n, const int64_t *base, const int32_t *ord, int64_t Vt, int64_t *pos,
-                       uint8_t *first_at) {
-  for (int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; j < Vt; j += (int64_t)gridDim.x * blockDim.x) {
-    const int a = input_of(base, n, j);
-    const int64_t i = j - base[a];
-    const uint16_t *s = in[a].tch + in[a].toff[i];
-    const int64_t ls = in[a].toff[i + 1] - in[a].toff[i];
-    int64_t r = i;
-    bool first = true;
-    for (int b = 0; b < n; b++) {
-      if (b == a || in[b].n == 0) continue;
-      const int64_t lb = term_bound(in[b], s, ls, false);
-      if (ord[b] < ord[a]) {
-        const int64_t ub = term_bound(in[b], s, ls, true);
-        r += ub;
-        if (ub > lb) first = false;
-      } else {
-        r += lb;
-      }
-    }
-    pos[j] = r;
-    first_at[r] = first ? 1 : 0;
-  }
-}
-// the segment at every rank position
-__global__ void k_segments(const InDev *in, int n, const int64_t *base, int64_t Vt, const int64_t *pos, int64_t *at_pos,
-                           int64_t *cnt_at, const int32_t **key, const int32_t **val, const uint8_t *first_at,
-                           int64_t *flag64) {
-  for (int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; j < Vt; j += (int64_t)gridDim.x * blockDim.x) {
-    const int a = input_of(base, n, j);
-    const int64_t i = j - base[a], r = pos[j], p0 = in[a].off[i];
-    at_pos[r] = j;
-    cnt_at[r] = in[a].off[i + 1] - p0;
-    key[r] = in[a].dn + p0;
-    val[r] = in[a].tf + p0;
-    flag64[j] = first_at[j];
-  }
-}
-// merged id of every segment, first segment of every merged term, old id -> merged
-// id of every input term, the length of every merged term's string, and the count
-// of merged terms that two or more inputs hold
-__global__ void k_merged_ids(const InDev *in, int n, const int64_t *base, const uint8_t *first_at, const int64_t *excl,
-                             const int64_t *at_pos, int64_t Vt, int32_t *gid, int64_t *gstart, int32_t *tmap,
-                             int64_t *glen, unsigned long long *shared) {
-  const int64_t span = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t r0 = blockIdx.x * (int64_t)blockDim.x; r0 < Vt; r0 += span) {
-    const int64_t r = r0 + threadIdx.x;
-    bool hit = false;
-    if (r < Vt) {
-      const int64_t g = excl[r] + first_at[r] - 1, j = at_pos[r];
-      gid[r] = (int32_t)g;
-      tmap[j] = (int32_t)g;
-      if (first_at[r]) {
-        const int a = input_of(base, n, j);
-        const int64_t i = j - base[a];
-        gstart[g] = r;
-        glen[g] = in[a].toff[i + 1] - in[a].toff[i];
-      } else {
-        hit = first_at[r - 1] != 0;  // the second source of its term
-      }
-    }
-    const unsigned long long m = __ballot(hit);
-    if ((threadIdx.x & 63) == 0 && m) atomicAdd(shared, (unsigned long long)__popcll(m));
-  }
-}
-// merged term strings from every term's first source: one wave per term
-__global__ void k_term_chars(const InDev *in, int n, const int64_t *base, const int64_t *gstart, const int64_t *at_pos,
-                             int64_t V, const int64_t *goff, uint16_t *gch) {
-  const int lane = threadIdx.x & 63;
-  const int64_t wpb = blockDim.x / 64;
-  for (int64_t g = blockIdx.x * wpb + (threadIdx.x >> 6); g < V; g += (int64_t)gridDim.x * wpb) {
-    const int64_t j = at_pos[gstart[g]];
-    const int a = input_of(base, n, j);
-    const int64_t i = j - base[a];
-    const uint16_t *s = in[a].tch + in[a].toff[i];
-    const int64_t l = goff[g + 1] - goff[g];
-    for (int64_t k = lane; k < l; k += 64) gch[goff[g] + k] = s[k];
-  }
-}
 
 // ---- tile boundaries ----------------------------------------------------------
 // Boundary t lies at diagonal t * T of the segments laid end to end: inside merged
@@ -449,48 +307,17 @@ __global__ __launch_bounds__(kNT) void k_tile_merge(Segs S, int T, int dedup, in
 // ---- the concatenation path: the segments laid end to end ARE the result ------
 __global__ __launch_bounds__(kNT) void k_concat(Segs S, int32_t *docno_d, int32_t *tf_d, uint32_t *oterm,
                                                 unsigned int *max_tf) {
-  __shared__ int64_t s_r[2];
-  const int64_t nblk = (S.total + 1023) / 1024;
   uint32_t mtf = 0;
-  for (int64_t b = blockIdx.x; b < nblk; b += gridDim.x) {
-    const int64_t p0 = b * 1024, p1 = min(S.total, p0 + 1024);
-    // the block's window of segments: its searches are bounded by the tile
-    if (threadIdx.x < 2) s_r[threadIdx.x] = last_le(S.pstart, 0, S.nseg + 1, threadIdx.x ? p1 - 1 : p0);
-    __syncthreads();
-    const int64_t w0 = s_r[0], w1 = s_r[1] + 1;
-    for (int64_t p = p0 + threadIdx.x; p < p1; p += kNT) {
-      const int64_t r = last_le(S.pstart, w0, w1, p), i = p - S.pstart[r];
-      const int32_t tf = S.val[r][i];
-      docno_d[p] = S.key[r][i];
-      tf_d[p] = tf;
-      oterm[p] = (uint32_t)S.gid[r];
-      mtf = max(mtf, (uint32_t)tf);
-    }
-    __syncthreads();
-  }
+  for_row_elements<kNT>(S.pstart, S.nseg, S.total, [&](int64_t p, int64_t r) {
+    const int64_t i = p - S.pstart[r];
+    const int32_t tf = S.val[r][i];
+    docno_d[p] = S.key[r][i];
+    tf_d[p] = tf;
+    oterm[p] = (uint32_t)S.gid[r];
+    mtf = max(mtf, (uint32_t)tf);
+  });
   for (int o = 32; o > 0; o >>= 1) mtf = max(mtf, (uint32_t)__shfl_xor((int)mtf, o, 64));
   if ((threadIdx.x & 63) == 0 && mtf) atomicMax(max_tf, mtf);
-}
-__global__ void k_concat_off(const int64_t *pstart, const int64_t *gstart, int64_t V, int64_t *off) {
-  for (int64_t g = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; g < V; g += (int64_t)gridDim.x * blockDim.x)
-    off[g] = pstart[gstart[g]];
-}
-
-// ---- reduce order past kTfSortMaxTf: stable by (term, tf desc) ----------------------
-__global__ void k_keys_term_tf(const uint32_t *term, const int32_t *tf, int64_t n, int tfb, uint32_t mtf, uint64_t *k,
-                               uint32_t *v) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    k[i] = ((uint64_t)term[i] << tfb) | (uint64_t)(mtf - (uint32_t)tf[i]);
-    v[i] = (uint32_t)i;
-  }
-}
-__global__ void k_gather_posts(const uint32_t *perm, const int32_t *dn, const int32_t *tf, int64_t n, int32_t *odn,
-                               int32_t *otf) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const uint32_t x = perm[i];
-    odn[i] = dn[x];
-    otf[i] = tf[x];
-  }
 }
 
 // ---- positions ------------------------------------------------------------------------
@@ -516,22 +343,13 @@ __global__ void k_ps_lens(const PsDev *ps, int n, const int64_t *rbase, const in
 __global__ __launch_bounds__(kNT) void k_ps_gather(const PsDev *ps, int n, const int64_t *rbase, const int64_t *tbase,
                                                    const int32_t *tmap, const int32_t *src, int64_t nrec,
                                                    const int64_t *ooff, int64_t M, int32_t *out) {
-  __shared__ int64_t s_r[2];
-  const int64_t nblk = (M + 1023) / 1024;
-  for (int64_t b = blockIdx.x; b < nblk; b += gridDim.x) {
-    const int64_t p0 = b * 1024, p1 = min(M, p0 + 1024);
-    if (threadIdx.x < 2) s_r[threadIdx.x] = last_le(ooff, 0, nrec + 1, threadIdx.x ? p1 - 1 : p0);
-    __syncthreads();
-    const int64_t w0 = s_r[0], w1 = s_r[1] + 1;
-    for (int64_t p = p0 + threadIdx.x; p < p1; p += kNT) {
-      const int64_t o = last_le(ooff, w0, w1, p), f = src[o];
-      const int a = input_of(rbase, n, f);
-      const int64_t i = f - rbase[a];
-      const int32_t id = ps[a].terms[ps[a].off[i] + (p - ooff[o])];
-      out[p] = id >= 0 ? tmap[tbase[a] + id] : id;
-    }
-    __syncthreads();
-  }
+  for_row_elements<kNT>(ooff, nrec, M, [&](int64_t p, int64_t o) {
+    const int64_t f = src[o];
+    const int a = input_of(rbase, n, f);
+    const int64_t i = f - rbase[a];
+    const int32_t id = ps[a].terms[ps[a].off[i] + (p - ooff[o])];
+    out[p] = id >= 0 ? tmap[tbase[a] + id] : id;
+  });
 }
 
 // the tiled merge of S: dedup (postings) -> count, scan, emit; else one emit pass.
@@ -597,13 +415,13 @@ sme_index *merge_indexes(sme_ctx *cx, sme_index *const *ins, int n, hipStream_t 
   for (auto &b : B) buf(b);
 
   // ---- the inputs
-  std::vector<InDev> hin((size_t)n);
+  std::vector<TermSource> hin((size_t)n);
   std::vector<int64_t> tbase((size_t)n + 1, 0), rbase((size_t)n + 1, 0);
   int64_t Pt = 0, N = 0, ps_total = 0, dmin = 0, dmax = -1;
   bool keep_ps = true, any_rec = false, any_ps = false;
   for (int a = 0; a < n; a++) {
     const sme_index *x = ins[a];
-    hin[(size_t)a] = InDev{(const int64_t *)x->d_term_off.p, (const uint16_t *)x->d_term_chars.p, x->V,
+    hin[(size_t)a] = TermSource{(const int64_t *)x->d_term_off.p, (const uint16_t *)x->d_term_chars.p, x->V,
                            (const int64_t *)x->d_off.p,      (const int32_t *)x->d_docno_d.p,     (const int32_t *)x->d_tf_d.p};
     tbase[(size_t)a + 1] = tbase[(size_t)a] + x->V;
     rbase[(size_t)a + 1] = rbase[(size_t)a] + x->N;
@@ -644,10 +462,10 @@ sme_index *merge_indexes(sme_ctx *cx, sme_index *const *ins, int n, hipStream_t 
       for (int i = 0; i < n; i++) ord[(size_t)by[(size_t)i]] = i;
   }
 
-  InDev *d_in = B[0].as<InDev>((size_t)n);
+  TermSource *d_in = B[0].as<TermSource>((size_t)n);
   int64_t *d_tbase = B[1].as<int64_t>((size_t)n + 1), *d_rbase = B[2].as<int64_t>((size_t)n + 1);
   int32_t *d_ord = B[3].as<int32_t>((size_t)n);
-  SME_HIP(hipMemcpyAsync(d_in, hin.data(), (size_t)n * sizeof(InDev), hipMemcpyHostToDevice, st));
+  SME_HIP(hipMemcpyAsync(d_in, hin.data(), (size_t)n * sizeof(TermSource), hipMemcpyHostToDevice, st));
   SME_HIP(hipMemcpyAsync(d_tbase, tbase.data(), ((size_t)n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
   SME_HIP(hipMemcpyAsync(d_rbase, rbase.data(), ((size_t)n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
   SME_HIP(hipMemcpyAsync(d_ord, ord.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, st));
@@ -671,44 +489,11 @@ sme_index *merge_indexes(sme_ctx *cx, sme_index *const *ins, int n, hipStream_t 
   }
 
   // ---------------- 1. terms ----------------
-  int64_t V = 0;
-  int64_t *pos = B[5].as<int64_t>((size_t)Vt + 1), *at_pos = B[6].as<int64_t>((size_t)Vt + 1);
-  uint8_t *first_at = B[7].as<uint8_t>((size_t)Vt + 1);
-  int64_t *cnt_at = B[8].as<int64_t>((size_t)Vt + 1), *pstart = B[9].as<int64_t>((size_t)Vt + 1);
-  int64_t *excl = B[10].as<int64_t>((size_t)Vt + 1);
-  const int32_t **seg_key = (const int32_t **)B[11].as<uint64_t>((size_t)Vt + 1);
-  const int32_t **seg_val = (const int32_t **)B[12].as<uint64_t>((size_t)Vt + 1);
-  int32_t *gid = B[13].as<int32_t>((size_t)Vt + 1), *tmap = B[14].as<int32_t>((size_t)Vt + 1);
-  int64_t *gstart = B[15].as<int64_t>((size_t)Vt + 2), *glen = B[16].as<int64_t>((size_t)Vt + 2);
-  if (Vt > 0) {
-    hipLaunchKernelGGL(k_rank, dim3(grid_n(Vt)), dim3(kNT), 0, st, d_in, n, d_tbase, d_ord, Vt, pos, first_at);
-    hipLaunchKernelGGL(k_segments, dim3(grid_n(Vt)), dim3(kNT), 0, st, d_in, n, d_tbase, Vt, pos, at_pos, cnt_at, seg_key,
-                       seg_val, first_at, excl);
-    SME_CHECK_LAUNCH();
-    excl_scan<int64_t>(excl, excl, Vt, B[17], st);
-    hipLaunchKernelGGL(k_merged_ids, dim3(grid_n(Vt)), dim3(kNT), 0, st, d_in, n, d_tbase, first_at, excl, at_pos, Vt,
-                       gid, gstart, tmap, glen, d_cnt);
-    SME_CHECK_LAUNCH();
-    V = (int64_t)rd1(gid + Vt - 1, st) + 1;
-  }
-  SME_HIP(hipMemsetAsync(cnt_at + Vt, 0, sizeof(int64_t), st));
-  excl_scan<int64_t>(cnt_at, pstart, Vt + 1, B[17], st);
-  SME_HIP(hipMemcpyAsync(gstart + V, &Vt, sizeof(int64_t), hipMemcpyHostToDevice, st));
-  ix->V = ix->Vt = V;
-  int64_t *term_off = ix->d_term_off.as<int64_t>((size_t)V + 1);
-  if (V > 0) {
-    SME_HIP(hipMemsetAsync(glen + V, 0, sizeof(int64_t), st));
-    excl_scan<int64_t>(glen, term_off, V + 1, B[17], st);
-    const int64_t tchars = rd1(term_off + V, st);
-    uint16_t *gch = ix->d_term_chars.as<uint16_t>((size_t)tchars + 1);
-    hipLaunchKernelGGL(k_term_chars, dim3(grid_n(V * 64)), dim3(kNT), 0, st, d_in, n, d_tbase, gstart, at_pos, V, term_off,
-                       gch);
-    SME_CHECK_LAUNCH();
-  } else {
-    SME_HIP(hipMemsetAsync(term_off, 0, sizeof(int64_t), st));
-    ix->d_term_chars.get(16);
-  }
-  SME_HIP(hipStreamSynchronize(st));  // (the host word gstart[V] was copied from)
+  const VocabUnion U = union_vocab(d_in, n, d_tbase, d_ord, Vt, ix, d_cnt,
+                                   UnionScratch{B[5], B[6], B[7], B[8], B[9], B[10], B[11], B[12], B[13], B[14], B[15],
+                                                B[16], B[17]},
+                                   st);
+  const int64_t V = U.V;
   prof.mark("terms");
 
   // ---------------- 2. docno-order postings ----------------
@@ -720,12 +505,10 @@ sme_index *merge_indexes(sme_ctx *cx, sme_index *const *ins, int n, hipStream_t 
   int32_t *docno_d = ix->d_docno_d.as<int32_t>((size_t)Pt + 1), *tf_d = ix->d_tf_d.as<int32_t>((size_t)Pt + 1);
   int mtf = 0;
   if (Pt > 0) {
-    Segs S{pstart, seg_key, seg_val, gid, gstart, Vt, V, Pt};
+    Segs S{U.pstart, U.seg_key, U.seg_val, U.gid, U.gstart, Vt, V, Pt};
     if (append) {
       hipLaunchKernelGGL(k_concat, dim3(grid_n(Pt, 1024, 65536)), dim3(kNT), 0, st, S, docno_d, tf_d, term_of, d_mtf);
-      hipLaunchKernelGGL(k_concat_off, dim3(grid_n(V)), dim3(kNT), 0, st, (const int64_t *)pstart,
-                         (const int64_t *)gstart, V, off);
-      SME_CHECK_LAUNCH();
+      segment_term_offsets(U.pstart, U.gstart, V, off, st);
       P = Pt;
     } else {
       P = tiled_merge(cx, S, T, true, docno_d, tf_d, term_of, off, d_mtf, d_err, B[19], B[20], B[21], B[22], B[23], B[17],
@@ -747,17 +530,7 @@ sme_index *merge_indexes(sme_ctx *cx, sme_index *const *ins, int n, hipStream_t 
     tf_sort_segments(off, V, P, docno_d, tf_d, ix->max_tf, docno_o, tf_o, B[24], B[25], B[26], B[17], d_cnt + 4,
                      st, cx->aux_stream, cx->ev_fork, cx->ev_join);
   } else if (P > 0) {
-    const int tfb = bits_of((uint64_t)ix->max_tf);
-    uint64_t *q0 = B[24].as<uint64_t>((size_t)P), *q1 = B[25].as<uint64_t>((size_t)P);
-    uint32_t *v0 = B[26].as<uint32_t>((size_t)P), *v1 = B[27].as<uint32_t>((size_t)P);
-    uint32_t *rscr = B[28].as<uint32_t>(kv_sort_scratch(P) / sizeof(uint32_t) + 1);
-    hipLaunchKernelGGL(k_keys_term_tf, dim3(grid_n(P)), dim3(kNT), 0, st, (const uint32_t *)term_of, (const int32_t *)tf_d,
-                       P, tfb, (uint32_t)ix->max_tf, q0, v0);
-    const uint32_t *fin =
-        kv_sort<uint64_t>(q0, v0, q1, v1, P, bits_of((uint64_t)std::max<int64_t>(V, 1)) + tfb, rscr, st);
-    hipLaunchKernelGGL(k_gather_posts, dim3(grid_n(P)), dim3(kNT), 0, st, fin, (const int32_t *)docno_d,
-                       (const int32_t *)tf_d, P, docno_o, tf_o);
-    SME_CHECK_LAUNCH();
+    sort_term_tf(term_of, docno_d, tf_d, nullptr, P, V, ix->max_tf, docno_o, tf_o, B[24], B[25], B[26], B[27], B[28], st);
   }
   prof.mark("tf_order");
 
@@ -812,7 +585,7 @@ sme_index *merge_indexes(sme_ctx *cx, sme_index *const *ins, int n, hipStream_t 
     int32_t *out = ix->d_ps_terms.as<int32_t>((size_t)M + 1);
     if (M > 0)
       hipLaunchKernelGGL(k_ps_gather, dim3(grid_n(M, 1024, 65536)), dim3(kNT), 0, st, d_ps, n, d_rbase, d_tbase,
-                         (const int32_t *)tmap, (const int32_t *)src, N, (const int64_t *)ooff, M, out);
+                         U.tmap, (const int32_t *)src, N, (const int64_t *)ooff, M, out);
     SME_CHECK_LAUNCH();
     ix->ps_records = N;
     ix->ps_terms = M;

@@ -19,7 +19,7 @@
 //             partition's end names the malformed record.
 //   keys      modified UTF-8 -> UTF-16, strict TermDF.compareTo order inside each
 //             partition, global rank = own index + lower bounds in the other
-//             partitions' sorted keys (as sme_merge.hip ranks shard pieces); a key
+//             partitions' sorted keys (as sme_vunion.hip ranks sources); a key
 //             found in another partition is refused.
 //   postings  one wave per term (tiles of 8192 postings for longer lists): big-
 //             endian (docno, tf) pairs at any byte alignment from aligned dword
@@ -41,6 +41,7 @@
 #include <string>
 
 #include "sme_internal.hpp"
+#include "sme_ixparts.hpp"
 #include "sme_recparse.hpp"
 
 namespace sme {
@@ -52,22 +53,6 @@ constexpr int kCandTile = 256 * kCandPer;    // per workgroup
 constexpr int64_t kBigDf = 8192;             // longer posting lists are decoded in tiles of this many
 constexpr int64_t kNxtEnd = -1, kNxtBad = -2;
 constexpr uint64_t kNoErr = ~0ull;
-
-unsigned grid_n(int64_t n, int nt = 256, int cap = 16384) {
-  return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + nt - 1) / nt, cap));
-}
-int bits_of(uint64_t v) {
-  int b = 1;
-  while (b < 64 && (1ull << b) <= v) b++;
-  return b;
-}
-template <typename T>
-T rd1(const T *d, hipStream_t st) {
-  T h;
-  SME_HIP(hipMemcpyAsync(&h, d, sizeof(T), hipMemcpyDeviceToHost, st));
-  SME_HIP(hipStreamSynchronize(st));
-  return h;
-}
 
 // partition p with po[p] <= x < po[p + 1] (x < po[np]; empty partitions skipped)
 __device__ __forceinline__ int part_of(const uint64_t *po, int np, uint64_t x) {
@@ -299,7 +284,7 @@ __device__ int64_t key_bound(const int64_t *uoff, const uint16_t *tch, int64_t r
   }
   return lo;
 }
-// order inside the partition, and the rank over all partitions (k_merge_rank's
+// order inside the partition, and the rank over all partitions (sme_vunion.hip's k_rank
 // scheme; here a key may be held by one partition only).  One thread per key: a
 // thread per (key, partition) with the counts summed by atomics was slower
 // (c2: 3.9 ms against 2.3).

@@ -13,9 +13,10 @@
 //          (the map task's doc-counter postings, TermKGramDocIndexer.java:84-90,126)
 //   (all_to_all of the blobs over RCCL / gloo, dist.reference_partitions)
 //   merge  (every owner)  the W received blobs -> one index holding the owned
-//          partitions' terms: term order = a rank by binary search of every
-//          term in the other pieces' sorted term lists (String.compareTo), equal
-//          strings -> one term; postings = MyReducer.reduce over the
+//          partitions' terms: term order = union_vocab (sme_vunion.hip, shared
+//          with sme_ixmerge.hip), a rank by binary search of every term in the
+//          other pieces' sorted term lists (String.compareTo), equal strings ->
+//          one term; postings = MyReducer.reduce over the
 //          concatenated map outputs: sorted by docno, equal docnos merged by
 //          summing tf (a docid duplicated across shards), stably sorted by tf
 //          desc; the doc counter = every map task's list, each starting at (0,0).
@@ -25,6 +26,7 @@
 #include <algorithm>
 
 #include "sme_internal.hpp"
+#include "sme_ixparts.hpp"
 
 namespace sme {
 
@@ -128,124 +130,26 @@ __global__ void k_pack_terms(const int32_t *sel, int64_t n, const int64_t *toff,
   }
 }
 
-struct PieceDev {  // a received piece's term list (device pointers)
-  const int64_t *toff;
-  const uint16_t *tch;
-  int64_t n;
-};
-
-// String.compareTo of units a[0, la) and b[0, lb)
-__device__ __forceinline__ int cmp_units(const uint16_t *a, int64_t la, const uint16_t *b, int64_t lb) {
-  const int64_t m = la < lb ? la : lb;
-  for (int64_t i = 0; i < m; i++)
-    if (a[i] != b[i]) return (int)a[i] - (int)b[i];
-  return la < lb ? -1 : (la > lb ? 1 : 0);
-}
-// first index of piece p whose term is >= s (upper: > s)
-__device__ int64_t piece_bound(const PieceDev &p, const uint16_t *s, int64_t ls, bool upper) {
-  int64_t lo = 0, hi = p.n;
-  while (lo < hi) {
-    const int64_t m = (lo + hi) >> 1;
-    const int c = cmp_units(p.tch + p.toff[m], p.toff[m + 1] - p.toff[m], s, ls);
-    if (c < 0 || (upper && c == 0))
-      lo = m + 1;
-    else
-      hi = m;
-  }
-  return lo;
-}
-// rank of every term of every piece in the merged sequence (equal strings
-// adjacent, in piece order); first: no earlier piece holds the string
-__global__ void k_merge_rank(const PieceDev *pcs, int np, const int64_t *base, int64_t Vt, int64_t *pos,
-                             uint8_t *first_at) {
-  for (int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; j < Vt; j += (int64_t)gridDim.x * blockDim.x) {
-    int a = 0;
-    while (a + 1 < np && base[a + 1] <= j) a++;
-    const int64_t i = j - base[a];
-    const PieceDev &pa = pcs[a];
-    const uint16_t *s = pa.tch + pa.toff[i];
-    const int64_t ls = pa.toff[i + 1] - pa.toff[i];
-    int64_t r = i;
-    bool first = true;
-    for (int b = 0; b < np; b++) {
-      if (b == a || pcs[b].n == 0) continue;
-      const int64_t lb = piece_bound(pcs[b], s, ls, false);
-      if (b < a) {
-        const int64_t ub = piece_bound(pcs[b], s, ls, true);
-        r += ub;
-        if (ub > lb) first = false;
-      } else {
-        r += lb;
-      }
-    }
-    pos[j] = r;
-    first_at[r] = first ? 1 : 0;
-  }
-}
-__global__ void k_merge_scatter(const PieceDev *pcs, int np, const int64_t *base, const int64_t *post_base,
-                                const int64_t *const *poff, int64_t Vt, const int64_t *pos, int64_t *at_pos,
-                                int64_t *cnt_at_pos) {
-  for (int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; j < Vt; j += (int64_t)gridDim.x * blockDim.x) {
-    int a = 0;
-    while (a + 1 < np && base[a + 1] <= j) a++;
-    const int64_t i = j - base[a];
-    at_pos[pos[j]] = j;
-    cnt_at_pos[pos[j]] = poff[a][i + 1] - poff[a][i];
-  }
-}
-// gid of every merged position: inclusive count of first flags - 1
-__global__ void k_gid_at(const uint8_t *first_at, const int64_t *excl, int64_t Vt, int64_t *gid_at) {
-  for (int64_t p = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; p < Vt; p += (int64_t)gridDim.x * blockDim.x)
-    gid_at[p] = excl[p] + first_at[p] - 1;
-}
 __global__ void k_first_flags_i64(const uint8_t *f, int64_t n, int64_t *v) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
     v[i] = f[i];
 }
-// merged term strings: the first occurrence of every gid; term lengths
-__global__ void k_gid_terms(const PieceDev *pcs, int np, const int64_t *base, const uint8_t *first_at,
-                            const int64_t *at_pos, const int64_t *gid_at, int64_t Vt, int64_t *src_j, int64_t *glen) {
-  for (int64_t p = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; p < Vt; p += (int64_t)gridDim.x * blockDim.x) {
-    if (!first_at[p]) continue;
-    const int64_t j = at_pos[p];
-    int a = 0;
-    while (a + 1 < np && base[a + 1] <= j) a++;
-    const int64_t i = j - base[a];
-    src_j[gid_at[p]] = j;
-    glen[gid_at[p]] = pcs[a].toff[i + 1] - pcs[a].toff[i];
-  }
-}
-__global__ void k_gid_chars(const PieceDev *pcs, int np, const int64_t *base, const int64_t *src_j, int64_t V,
-                            const int64_t *goff, uint16_t *gch) {
-  const int lane = threadIdx.x & 63;
-  const int64_t wpb = blockDim.x / 64;
-  for (int64_t g = blockIdx.x * wpb + (threadIdx.x >> 6); g < V; g += (int64_t)gridDim.x * wpb) {
-    const int64_t j = src_j[g];
-    int a = 0;
-    while (a + 1 < np && base[a + 1] <= j) a++;
-    const int64_t i = j - base[a];
-    const uint16_t *s = pcs[a].tch + pcs[a].toff[i];
-    const int64_t l = goff[g + 1] - goff[g];
-    for (int64_t k = lane; k < l; k += 64) gch[goff[g] + k] = s[k];
-  }
-}
-// postings of every piece term into its merged slot: one wave per term
-__global__ void k_merge_postings(int np, const int64_t *base, const int64_t *const *poff, const int32_t *const *pdn,
-                                 const int32_t *const *ptf, int64_t Vt, const int64_t *pos, const int64_t *pstart_at,
-                                 const int64_t *gid_at, int32_t *cdn, int32_t *ctf, uint32_t *cgid,
-                                 unsigned int *max_tf) {
+// postings of every piece term into its merged slot: one wave per term (what
+// sme_ixmerge.hip's k_concat computes flat; the two are equivalent)
+__global__ void k_merge_postings(const TermSource *in, int np, const int64_t *base, int64_t Vt, const int64_t *pos,
+                                 const int64_t *pstart_at, const int32_t *gid_at, int32_t *cdn, int32_t *ctf,
+                                 uint32_t *cgid, unsigned int *max_tf) {
   const int lane = threadIdx.x & 63;
   const int64_t wpb = blockDim.x / 64;
   uint32_t m = 0;
   for (int64_t j = blockIdx.x * wpb + (threadIdx.x >> 6); j < Vt; j += (int64_t)gridDim.x * wpb) {
-    int a = 0;
-    while (a + 1 < np && base[a + 1] <= j) a++;
+    const int a = input_of(base, np, j);
     const int64_t i = j - base[a];
-    const int64_t p0 = poff[a][i], pl = poff[a][i + 1] - p0, d0 = pstart_at[pos[j]];
+    const int64_t p0 = in[a].off[i], pl = in[a].off[i + 1] - p0, d0 = pstart_at[pos[j]];
     const uint32_t g = (uint32_t)gid_at[pos[j]];
     for (int64_t k = lane; k < pl; k += 64) {
-      const int32_t tf = ptf[a][p0 + k];
-      cdn[d0 + k] = pdn[a][p0 + k];
+      const int32_t tf = in[a].tf[p0 + k];
+      cdn[d0 + k] = in[a].dn[p0 + k];
       ctf[d0 + k] = tf;
       cgid[d0 + k] = g;
       m = max(m, (uint32_t)tf);
@@ -253,11 +157,6 @@ __global__ void k_merge_postings(int np, const int64_t *base, const int64_t *con
   }
   for (int o = 32; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o, 64));
   if (lane == 0 && m) atomicMax(max_tf, m);
-}
-__global__ void k_gid_offsets(const uint8_t *first_at, const int64_t *gid_at, const int64_t *pstart_at, int64_t Vt,
-                              int64_t *off) {
-  for (int64_t p = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; p < Vt; p += (int64_t)gridDim.x * blockDim.x)
-    if (first_at[p]) off[gid_at[p]] = pstart_at[p];
 }
 __global__ void k_keys_docno(const int32_t *dn, int64_t n, uint32_t *k, uint32_t *v) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
@@ -294,23 +193,6 @@ __global__ void k_count_gid(const uint32_t *gid, int64_t n, int64_t *off) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
     if (i == 0 || gid[i] != gid[i - 1]) off[gid[i]] = i;
 }
-// (gid, tf desc) keys of the items in `perm` order (perm: nullptr = identity)
-__global__ void k_keys_gid_tf(const uint32_t *gid, const int32_t *tf, const uint32_t *perm, int64_t n, int tfb,
-                              uint32_t mtf, uint64_t *k, uint32_t *v) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const uint32_t x = perm ? perm[i] : (uint32_t)i;
-    k[i] = ((uint64_t)gid[x] << tfb) | (uint64_t)(mtf - (uint32_t)tf[x]);
-    v[i] = x;
-  }
-}
-__global__ void k_gather_posts(const uint32_t *perm, const int32_t *dn, const int32_t *tf, int64_t n, int32_t *odn,
-                               int32_t *otf) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const uint32_t x = perm[i];
-    odn[i] = dn[x];
-    otf[i] = tf[x];
-  }
-}
 __global__ void k_max_i32(const int32_t *a, int64_t n, unsigned int *mx) {
   uint32_t m = 0;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
@@ -324,22 +206,6 @@ __global__ void k_split_firsts(const int64_t *rbase, int np, int64_t N, uint8_t 
     for (int a = 0; a < np; a++) f |= rbase[a] == i && rbase[a + 1] > i;
     first[i] = f;
   }
-}
-
-unsigned grid_n(int64_t n, int nt = 256, int cap = 16384) {
-  return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + nt - 1) / nt, cap));
-}
-int bits_of(uint64_t v) {
-  int b = 1;
-  while (b < 64 && (1ull << b) <= v) b++;
-  return b;
-}
-template <typename T>
-T rd1(const T *d, hipStream_t st) {
-  T h;
-  SME_HIP(hipMemcpyAsync(&h, d, sizeof(T), hipMemcpyDeviceToHost, st));
-  SME_HIP(hipStreamSynchronize(st));
-  return h;
 }
 
 }  // namespace
@@ -444,18 +310,16 @@ sme_index *merge_pieces(sme_ctx *cx, const uint8_t *d_blobs, const uint64_t *siz
       throw Error(SME_EINVAL, "pieces of different k-gram lengths");
     at += lay[a].total;
   }
-  std::vector<PieceDev> hp(np);
+  std::vector<TermSource> hp(np);
   std::vector<int64_t> base(np + 1, 0), pbase(np + 1, 0), rbase(np + 1, 0);
-  std::vector<const int64_t *> hpoff(np);
-  std::vector<const int32_t *> hpdn(np), hptf(np);
+  std::vector<int32_t> ord(np);  // the union's source order: the pieces'
   bool ordered = true;  // record docno ranges disjoint and increasing with the piece index
   int64_t last_max = INT64_MIN;
   for (int a = 0; a < np; a++) {
-    hp[a] = PieceDev{(const int64_t *)(bp[a] + lay[a].term_off), (const uint16_t *)(bp[a] + lay[a].term_chars),
-                     hd[a].nterms};
-    hpoff[a] = (const int64_t *)(bp[a] + lay[a].post_off);
-    hpdn[a] = (const int32_t *)(bp[a] + lay[a].docno);
-    hptf[a] = (const int32_t *)(bp[a] + lay[a].tf);
+    hp[a] = TermSource{(const int64_t *)(bp[a] + lay[a].term_off), (const uint16_t *)(bp[a] + lay[a].term_chars),
+                       hd[a].nterms, (const int64_t *)(bp[a] + lay[a].post_off), (const int32_t *)(bp[a] + lay[a].docno),
+                       (const int32_t *)(bp[a] + lay[a].tf)};
+    ord[a] = a;
     base[a + 1] = base[a] + hd[a].nterms;
     pbase[a + 1] = pbase[a] + hd[a].npost;
     rbase[a + 1] = rbase[a] + hd[a].nrec;
@@ -465,18 +329,17 @@ sme_index *merge_pieces(sme_ctx *cx, const uint8_t *d_blobs, const uint64_t *siz
     }
   }
   const int64_t Vt = base[np], Pt = pbase[np], N = rbase[np];
+  // merged ids and posting places are 32-bit
+  if (Pt > 0xFFFFFFFFll) throw Error(SME_ELIMIT, "piece merge: more than 2^32 postings");
+  if (Vt > 0x7FFFFFFFll) throw Error(SME_ELIMIT, "piece merge: 2^31 or more terms");
   // small device tables of the pieces
-  PieceDev *d_pcs = W[10].as<PieceDev>(np);
+  TermSource *d_pcs = W[10].as<TermSource>(np);
   int64_t *d_base = W[11].as<int64_t>(np + 1);
-  const int64_t **d_poff = (const int64_t **)W[12].as<uint64_t>(np);
-  const int32_t **d_pdn = (const int32_t **)W[13].as<uint64_t>(np);
-  const int32_t **d_ptf = (const int32_t **)W[14].as<uint64_t>(np);
+  int32_t *d_ord = W[12].as<int32_t>(np);
   int64_t *d_rbase = W[15].as<int64_t>(np + 1);
-  SME_HIP(hipMemcpyAsync(d_pcs, hp.data(), np * sizeof(PieceDev), hipMemcpyHostToDevice, st));
+  SME_HIP(hipMemcpyAsync(d_pcs, hp.data(), np * sizeof(TermSource), hipMemcpyHostToDevice, st));
   SME_HIP(hipMemcpyAsync(d_base, base.data(), (np + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
-  SME_HIP(hipMemcpyAsync(d_poff, hpoff.data(), np * sizeof(void *), hipMemcpyHostToDevice, st));
-  SME_HIP(hipMemcpyAsync(d_pdn, hpdn.data(), np * sizeof(void *), hipMemcpyHostToDevice, st));
-  SME_HIP(hipMemcpyAsync(d_ptf, hptf.data(), np * sizeof(void *), hipMemcpyHostToDevice, st));
+  SME_HIP(hipMemcpyAsync(d_ord, ord.data(), np * sizeof(int32_t), hipMemcpyHostToDevice, st));
   SME_HIP(hipMemcpyAsync(d_rbase, rbase.data(), (np + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
 
   sme_index *ix = new sme_index(cx);
@@ -488,55 +351,24 @@ sme_index *merge_pieces(sme_ctx *cx, const uint8_t *d_blobs, const uint64_t *siz
   ix->idf_mode = cx->cfg.idf_mode;
   ix->records_only = true;
   ix->N = N;
-  // 1. merged vocabulary
-  int64_t V = 0;
-  int64_t *pos = W[16].as<int64_t>(Vt + 1);
-  uint8_t *first_at = W[17].as<uint8_t>(Vt + 1);
-  int64_t *at_pos = W[18].as<int64_t>(Vt + 1), *cnt_at = W[19].as<int64_t>(Vt + 1);
-  int64_t *excl = W[20].as<int64_t>(Vt + 1), *gid_at = W[21].as<int64_t>(Vt + 1);
-  int64_t *pstart = W[22].as<int64_t>(Vt + 1);
-  if (Vt > 0) {
-    hipLaunchKernelGGL(k_merge_rank, dim3(grid_n(Vt)), dim3(256), 0, st, d_pcs, np, d_base, Vt, pos, first_at);
-    hipLaunchKernelGGL(k_merge_scatter, dim3(grid_n(Vt)), dim3(256), 0, st, d_pcs, np, d_base, (const int64_t *)nullptr,
-                       d_poff, Vt, pos, at_pos, cnt_at);
-    hipLaunchKernelGGL(k_first_flags_i64, dim3(grid_n(Vt)), dim3(256), 0, st, first_at, Vt, excl);
-    excl_scan(excl, excl, Vt, W[23], st);
-    hipLaunchKernelGGL(k_gid_at, dim3(grid_n(Vt)), dim3(256), 0, st, first_at, excl, Vt, gid_at);
-    SME_CHECK_LAUNCH();
-    V = rd1(gid_at + Vt - 1, st) + 1;
-  }
-  ix->V = ix->Vt = V;
-  int64_t *term_off = ix->d_term_off.as<int64_t>(V + 1);
-  if (V > 0) {
-    int64_t *src_j = W[24].as<int64_t>(V + 1), *glen = W[25].as<int64_t>(V + 1);
-    hipLaunchKernelGGL(k_gid_terms, dim3(grid_n(Vt)), dim3(256), 0, st, d_pcs, np, d_base, first_at, at_pos, gid_at, Vt,
-                       src_j, glen);
-    SME_HIP(hipMemsetAsync(glen + V, 0, sizeof(int64_t), st));
-    excl_scan(glen, term_off, V + 1, W[23], st);
-    const int64_t tchars = rd1(term_off + V, st);
-    uint16_t *gch = ix->d_term_chars.as<uint16_t>(tchars + 1);
-    hipLaunchKernelGGL(k_gid_chars, dim3(grid_n(V * 64)), dim3(256), 0, st, d_pcs, np, d_base, src_j, V, term_off, gch);
-    SME_CHECK_LAUNCH();
-  } else {
-    SME_HIP(hipMemsetAsync(term_off, 0, sizeof(int64_t), st));
-    ix->d_term_chars.get(16);
-  }
+  // 1. merged vocabulary: union_vocab (sme_vunion.hip), the pieces in order
+  const VocabUnion U = union_vocab(d_pcs, np, d_base, d_ord, Vt, ix, nullptr,
+                                   UnionScratch{W[16], W[18], W[17], W[19], W[22], W[20], W[13], W[14], W[21], W[0],
+                                                W[24], W[25], W[23]},
+                                   st);
+  const int64_t V = U.V;
   // 2. postings grouped by merged term (pieces in order inside a term)
   int64_t P = Pt;
   int64_t *off = ix->d_off.as<int64_t>(V + 1);
-  int32_t *docno_o = nullptr, *tf_o = nullptr;
   int32_t mtf = 0;
   if (Pt > 0) {
-    SME_HIP(hipMemsetAsync(cnt_at + Vt, 0, sizeof(int64_t), st));
-    excl_scan(cnt_at, pstart, Vt + 1, W[23], st);
     int32_t *cdn = W[26].as<int32_t>(Pt), *ctf = W[27].as<int32_t>(Pt);
     uint32_t *cgid = W[28].as<uint32_t>(Pt);
     unsigned int *d_mtf = W[3].as<unsigned int>(4);
     SME_HIP(hipMemsetAsync(d_mtf, 0, sizeof(unsigned int), st));
-    hipLaunchKernelGGL(k_merge_postings, dim3(grid_n(Vt * 64)), dim3(256), 0, st, np, d_base, d_poff, d_pdn, d_ptf, Vt,
-                       pos, pstart, gid_at, cdn, ctf, cgid, d_mtf);
+    hipLaunchKernelGGL(k_merge_postings, dim3(grid_n(Vt * 64)), dim3(256), 0, st, (const TermSource *)d_pcs, np,
+                       (const int64_t *)d_base, Vt, U.pos, U.pstart, U.gid, cdn, ctf, cgid, d_mtf);
     SME_CHECK_LAUNCH();
-    const uint32_t *perm = nullptr;  // item order so far (nullptr: the grouped order)
     uint32_t *k0 = W[29].as<uint32_t>(Pt), *k1 = W[30].as<uint32_t>(Pt);
     uint32_t *v0 = W[31].as<uint32_t>(Pt), *v1 = W[32].as<uint32_t>(Pt);
     uint32_t *rscr = W[33].as<uint32_t>(kv_sort_scratch(Pt) / sizeof(uint32_t) + 1);
@@ -576,20 +408,12 @@ sme_index *merge_pieces(sme_ctx *cx, const uint8_t *d_blobs, const uint64_t *siz
       mtf = (int32_t)rd1(d_mtf, st);
     } else {
       mtf = (int32_t)rd1(d_mtf, st);
-      hipLaunchKernelGGL(k_gid_offsets, dim3(grid_n(Vt)), dim3(256), 0, st, first_at, gid_at, pstart, Vt, off);
+      segment_term_offsets(U.pstart, U.gstart, V, off, st);
     }
     SME_HIP(hipMemcpyAsync(off + V, &P, sizeof(int64_t), hipMemcpyHostToDevice, st));
     // stable by (term, tf desc): the reducer's final Collections.sort (:211)
-    const int tfb = bits_of((uint64_t)std::max(mtf, 1));
-    uint64_t *q0 = W[39].as<uint64_t>(P), *q1 = W[40].as<uint64_t>(P);
-    hipLaunchKernelGGL(k_keys_gid_tf, dim3(grid_n(P)), dim3(256), 0, st, cgid, ctf, perm, P, tfb, (uint32_t)mtf, q0,
-                       v0);
-    const uint32_t *fin = kv_sort<uint64_t>(q0, v0, q1, v1, P, bits_of((uint64_t)std::max<int64_t>(V, 1)) + tfb, rscr,
-                                            st);
-    docno_o = ix->d_docno_o.as<int32_t>(P + 1);
-    tf_o = ix->d_tf_o.as<int32_t>(P + 1);
-    hipLaunchKernelGGL(k_gather_posts, dim3(grid_n(P)), dim3(256), 0, st, fin, cdn, ctf, P, docno_o, tf_o);
-    SME_CHECK_LAUNCH();
+    sort_term_tf(cgid, cdn, ctf, nullptr, P, V, mtf, ix->d_docno_o.as<int32_t>(P + 1), ix->d_tf_o.as<int32_t>(P + 1),
+                 W[39], W[40], W[31], W[32], W[33], st);
   } else {
     SME_HIP(hipMemsetAsync(off, 0, (V + 1) * sizeof(int64_t), st));
     ix->d_docno_o.get(16);

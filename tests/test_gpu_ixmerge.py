@@ -367,6 +367,29 @@ def test_paths_identical(sme):
     _raises(lambda: ctx.set_option("merge_append", 2), SME_EINVAL)
 
 
+# ---- 4b. the two mergers on one vocabulary union ---------------------------------------------
+UNION_CASES = ([("share", X.share_case), ("three", X.three_input_case), ("duplicate", X.duplicate_case)] +
+               [("empty%d" % i, lambda i=i: X.empty_input_cases()[i]) for i in range(3)] +
+               [("tiny64", lambda: X.tiny_inputs_case(64))])
+
+
+@pytest.mark.parametrize("name,case", UNION_CASES, ids=[n for n, _ in UNION_CASES])
+def test_piece_merge_equals_index_merge(sme, name, case):
+    """merge_pieces over world-1 pieces of inputs whose docnos interleave (its sort and
+    dedup path, never taken by contiguous pieces) writes the record stream of ctx.merge."""
+    import torch
+    ctx = _ctx(sme, _edge_mapping(), 2, 1)
+    inputs = [ctx.build(X.corpus_bytes(docs) or b"text outside every record\n") for docs in case()]
+    sizes = [p.pack_pieces(1)[0] for p in inputs]
+    blob = torch.empty(max(sum(sizes), 16), dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+    at = 0
+    for p, s in zip(inputs, sizes):
+        p.pack_pieces(1, blob.data_ptr() + at)
+        at += s
+    assert _all_records(ctx.merge_pieces(blob.data_ptr(), sizes)) == _all_records(ctx.merge(inputs))
+
+
 # ---- 5. mixed inputs ----------------------------------------------------------------------
 def test_mixed_inputs(sme):
     c, mb = _corpus("fuzz")
