@@ -170,6 +170,8 @@ void sme_destroy(sme_ctx *ctx);
  *   "merge_append"  sme_index_merge: 1 (default) inputs whose docno ranges are pairwise disjoint
  *                   are laid end to end without merging, 0 every call takes the general merge.
  *                   Results are the same
+ *   "bm25_split"    sme_query_topk_bm25*: scorer workgroups per query, 0 (default) automatic,
+ *                   >= 1 that many (capped at the window count and at 4096).  Results are the same
  * Unknown names and out-of-range values are SME_EINVAL. */
 int sme_set_option(sme_ctx *ctx, const char *name, int64_t value);
 
@@ -758,6 +760,62 @@ int sme_query_topk_device(sme_index *ix, const int32_t *d_term_ids, const int64_
 int sme_query_topk_device_tie(sme_index *ix, const int32_t *d_term_ids, const int64_t *d_q_offsets,
                               int nq, int k, int32_t *d_out_docno, double *d_out_score, uint32_t *d_out_tie,
                               void *stream);
+
+/* BM25 ranking.  For an index with a query side (a records-only merged index and
+ * a chargram output are SME_EINVAL, as the other query entries refuse them).
+ *
+ * Collection statistics, from the docno-order postings alone (so a built, a loaded,
+ * a merged and a deleted-from index have them alike, and sme_index_reweight does
+ * not touch them):
+ *   dl[d]   the sum of tf over all postings whose docno is d (an int64 sum stored as
+ *           int32; a length that does not fit is SME_ELIMIT): for K = 1 the number of
+ *           index terms in the document's records, DOCNO tokens included, for K >= 2
+ *           the number of grams.  The " " doc-counter record is no posting list here.
+ *   D       the docnos with at least one posting;  L = sum of dl;
+ *   avgdl   (double)L / (double)D;
+ *   df_t    the postings of term t: the true df, whatever the index's idf mode.
+ * Weights, all fp64 in exactly this association (no fused multiply-add):
+ *   idf_t   = log(1.0 + ((double)(D - df_t) + 0.5) / ((double)df_t + 0.5)), natural log
+ *             with the bits of the HOST's libm (a table by df, gathered on the device)
+ *   norm_d  = k1 * ((1.0 - b) + b * ((double)dl[d] / avgdl))
+ *   w(t, d) = idf_t * (((double)tf * (k1 + 1.0)) / ((double)tf + norm_d))
+ * A document's score starts at 0.0 and adds w over the query's term slots in listed
+ * order: a slot whose list lacks the document adds nothing, a term listed twice
+ * counts twice, -1 slots are skipped.  Results are laid out as sme_query_topk's: k
+ * rows per query by score descending, then docno ascending (signed), padded with
+ * docno -1 / score 0.0; a document holding none of the terms is never a result, and
+ * D == 0, an empty query and a query of -1 slots only give pads.
+ * k1 must be finite and >= 0 and b in [0, 1]: anything else, NaN included, is
+ * SME_EINVAL.  Limits (SME_ELIMIT, the message names the query): k <= 1024, and at
+ * most 1024 term slots per query.  An id outside [-1, V) is SME_EINVAL from the host
+ * entry (the query named) and skipped like -1 by the device entry; offsets that do
+ * not ascend from 0, k < 1 and nq < 0 are SME_EINVAL.
+ *
+ * The scorer is window-major over windows of 1024 docnos (sme_index_bm25_stats's
+ * *window) and exhaustive inside a window; once k candidates stand, a window whose
+ * bound -- every slot's weight at the term's largest tf in a document as short as
+ * the window's shortest -- lies strictly below the k-th score is skipped.  Option
+ * "bm25_split": workgroups per query, 0 (default) automatic, >= 1 that many, capped
+ * at the window count and at 4096.  Results are the same for every value.
+ *
+ * sme_index_prepare_bm25 builds the index's tables (dl, idf, the bound tables) once;
+ * nothing ever invalidates them, and the other entries build them on first use.
+ * *ms (may be NULL) gets the device time.  sme_index_doc_lengths: the device pointer
+ * of dl[docno - *dmin], *span entries, 0 for a docno without postings; the index's
+ * own array.  sme_index_bm25_stats: D, L, the longest document, the window size.
+ * sme_query_bm25_stats reports on the last BM25 call: the (query, window) pairs that
+ * held a posting, those of them the bound skipped, and the postings scored (under a
+ * split the workgroups of a query share the k-th score as they find it, so timing
+ * may move the last two; it never moves a result). */
+int sme_index_prepare_bm25(sme_index *ix, void *stream, float *ms);
+int sme_index_doc_lengths(sme_index *ix, void *stream, const int32_t **d_len, int64_t *dmin, int64_t *span);
+int sme_index_bm25_stats(const sme_index *ix, uint64_t *docs, uint64_t *total_len, uint64_t *max_len,
+                         uint64_t *window);
+int sme_query_topk_bm25(sme_index *ix, const int32_t *term_ids, const int64_t *q_offsets, int nq, int k, double k1,
+                        double b, int32_t *out_docno, double *out_score);
+int sme_query_topk_bm25_device(sme_index *ix, const int32_t *d_term_ids, const int64_t *d_q_offsets, int nq, int k,
+                               double k1, double b, int32_t *d_out_docno, double *d_out_score, void *stream);
+int sme_query_bm25_stats(const sme_index *ix, uint64_t *windows, uint64_t *skipped, uint64_t *postings);
 
 /* 128-bit fingerprint of every index term (two u64 per term into device memory
  * d_out[2 V]): equal term strings (k-grams) on different shards get equal

@@ -64,6 +64,8 @@ EXPORTS = [
     "sme_index_delete_docnos", "sme_index_delete_docnos_device", "sme_index_delete_stats",
     "sme_index_positions_file", "sme_index_positions_file_device", "sme_index_attach_positions",
     "sme_index_attach_positions_device", "sme_index_posfile_stats",
+    "sme_index_prepare_bm25", "sme_index_doc_lengths", "sme_index_bm25_stats", "sme_query_topk_bm25",
+    "sme_query_topk_bm25_device", "sme_query_bm25_stats",
 ]
 
 
@@ -188,6 +190,13 @@ def lib():
     L.sme_index_attach_positions.argtypes = [vp, vp, sz, C.c_int, vp]
     L.sme_index_attach_positions_device.argtypes = [vp, vp, sz, C.c_int, vp]
     L.sme_index_posfile_stats.argtypes = [vp] + [C.POINTER(C.c_uint64)] * 3 + [C.POINTER(C.c_float)] * 3
+    L.sme_index_prepare_bm25.argtypes = [vp, vp, C.POINTER(C.c_float)]
+    L.sme_index_doc_lengths.argtypes = [vp, vp, C.POINTER(vp), i64p, i64p]
+    L.sme_index_bm25_stats.argtypes = [vp] + [C.POINTER(C.c_uint64)] * 4
+    L.sme_query_topk_bm25.argtypes = [vp, i32p, i64p, C.c_int, C.c_int, C.c_double, C.c_double, i32p,
+                                      C.POINTER(C.c_double)]
+    L.sme_query_topk_bm25_device.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_double, C.c_double, vp, vp, vp]
+    L.sme_query_bm25_stats.argtypes = [vp] + [C.POINTER(C.c_uint64)] * 3
     _lib = L
     return L
 
@@ -1057,6 +1066,61 @@ class Index:
         return {"file_bytes": u[0].value, "bits": u[1].value, "checked_postings": u[2].value,
                 "encode_ms": f[0].value, "decode_ms": f[1].value, "crosscheck_ms": f[2].value}
 
+    # ---- BM25 ranking (include/sme.h, sme_query_topk_bm25)
+    def prepare_bm25(self, stream=None):
+        """Build the BM25 tables (document lengths, idf by true df, the bound tables)
+        now (else the first BM25 call does); returns their device build time in ms."""
+        ms = C.c_float(0.0)
+        _check(lib().sme_index_prepare_bm25(self._h, C.c_void_p(stream or 0), C.byref(ms)))
+        return ms.value
+
+    def doc_lengths_device(self, stream=None):
+        """(device pointer of int32 dl[docno - dmin], dmin, span): the index's own array."""
+        p, dmin, span = C.c_void_p(), C.c_int64(), C.c_int64()
+        _check(lib().sme_index_doc_lengths(self._h, C.c_void_p(stream or 0), C.byref(p), C.byref(dmin), C.byref(span)))
+        return p.value or 0, dmin.value, span.value
+
+    def doc_lengths(self):
+        """(dmin, np.int32[span]): dl[docno - dmin], the sum of tf over the document's
+        postings, 0 for a docno without postings."""
+        p, dmin, span = self.doc_lengths_device()
+        dl = np.zeros(span, np.int32)
+        if span:
+            _d2h(dl, p, 4 * span)
+        return dmin, dl
+
+    def bm25_stats(self):
+        """{"docs": D, "total_len": L, "max_len", "window": documents per scorer window}."""
+        d, t, m, w = Index._stats(self._h, lib().sme_index_bm25_stats, 4)
+        return {"docs": d, "total_len": t, "max_len": m, "window": w}
+
+    def query_bm25(self, term_ids, q_offsets, k=10, k1=1.2, b=0.75):
+        """Batched BM25 ranking, laid out as query_topk: (docno[nq,k], score[nq,k]) by
+        score descending then docno ascending; docno -1 / score 0.0 pad."""
+        term_ids = np.ascontiguousarray(term_ids, dtype=np.int32)
+        q_offsets = np.ascontiguousarray(q_offsets, dtype=np.int64)
+        nq = len(q_offsets) - 1
+        rows = max(nq, 1) * max(int(k), 1)
+        dn = np.zeros(rows, dtype=np.int32)
+        sc = np.zeros(rows, dtype=np.float64)
+        keep, ptrs = Index._typed_ptrs([term_ids, q_offsets], (np.int32, np.int64))
+        _check(lib().sme_query_topk_bm25(self._h, ptrs[0], ptrs[1], nq, int(k), float(k1), float(b),
+                                         dn.ctypes.data_as(C.POINTER(C.c_int32)),
+                                         sc.ctypes.data_as(C.POINTER(C.c_double))))
+        return dn[:nq * k].reshape(nq, k), sc[:nq * k].reshape(nq, k)
+
+    def query_bm25_device(self, d_terms, d_qoff, nq, k, d_out_docno, d_out_score, k1=1.2, b=0.75, stream=None):
+        """query_bm25 with every array in device memory (query_topk_device's layout)."""
+        _check(lib().sme_query_topk_bm25_device(self._h, C.c_void_p(d_terms), C.c_void_p(d_qoff), nq, int(k),
+                                                float(k1), float(b), C.c_void_p(d_out_docno),
+                                                C.c_void_p(d_out_score), C.c_void_p(stream or 0)))
+
+    def query_bm25_stats(self):
+        """The last BM25 call: {"windows": (query, window) pairs that held a posting,
+        "skipped": those the bound skipped, "postings": postings scored}."""
+        w, s, p = Index._stats(self._h, lib().sme_query_bm25_stats, 3)
+        return {"windows": w, "skipped": s, "postings": p}
+
     def reweight(self, n_global, d_df_global=None, stream=None):
         """TF-IDF weights with all-reduced N (and df) of a doc-sharded index."""
         _check(lib().sme_index_reweight(self._h, n_global, C.c_void_p(d_df_global or 0), C.c_void_p(stream or 0)))
@@ -1515,6 +1579,14 @@ class IntDocVectorsForwardIndex:
         if not self._terms:
             return []
         dn, _ = self.index.query_topk(np.array(self._terms, np.int32), np.array([0, len(self._terms)], np.int64), k)
+        return [int(d) for d in dn[0] if d >= 0]
+
+    def rank_bm25(self, k=10, k1=1.2, b=0.75):
+        """rank() by BM25 score (Index.query_bm25) over the terms getValue set."""
+        if not self._terms:
+            return []
+        dn, _ = self.index.query_bm25(np.array(self._terms, np.int32), np.array([0, len(self._terms)], np.int64), k,
+                                      k1, b)
         return [int(d) for d in dn[0] if d >= 0]
 
     def query_line(self, line, tokenizer=None):

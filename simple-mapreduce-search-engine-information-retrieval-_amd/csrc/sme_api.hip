@@ -11,6 +11,7 @@
 #include <system_error>
 #include <thread>
 
+#include "sme_bm25.hpp"
 #include "sme_feedback.hpp"
 #include "sme_internal.hpp"
 #include "sme_ixmerge.hpp"
@@ -386,6 +387,9 @@ int sme_set_option(sme_ctx *cx, const char *name, int64_t v) {
     } else if (n == "merge_append") {
       range(0, 1);
       cx->opt_merge_append = v;
+    } else if (n == "bm25_split") {
+      range(0, int64_t(1) << 30);
+      cx->opt_bm25_split = v;
     } else {
       throw sme::Error(SME_EINVAL, "unknown option " + n);
     }
@@ -1272,6 +1276,125 @@ int sme_query_topk_tie(sme_index *ix, const int32_t *term_ids, const int64_t *q_
                        int32_t *out_docno, double *out_score, uint32_t *out_tie) {
   if (nq > 0 && !out_tie) return fail(SME_EINVAL, "null argument");
   return query_topk_host(ix, term_ids, q_offsets, nq, k, out_docno, out_score, out_tie);
+}
+
+// BM25 ranking runs over the query side of a TermKGramDocIndexer index
+static void need_bm25_index(const sme_index *ix) {
+  if (!ix) throw sme::Error(SME_EINVAL, "null index");
+  if (ix->job != 0) throw sme::Error(SME_EINVAL, "bm25: a CharKGramTermIndexer output has no postings by document");
+  if (ix->records_only)
+    throw sme::Error(SME_EINVAL, "bm25: records-only index (merged shard pieces): query the shard indexes");
+}
+
+int sme_index_prepare_bm25(sme_index *ix, void *stream, float *ms) {
+  return guard([&] {
+    need_bm25_index(ix);
+    set_device(ix->ctx);
+    sme::prepare_bm25(ix, stream_of(ix->ctx, stream));
+    if (ms) *ms = ix->bm_ms;
+  });
+}
+
+int sme_index_doc_lengths(sme_index *ix, void *stream, const int32_t **d_len, int64_t *dmin, int64_t *span) {
+  return guard([&] {
+    need_bm25_index(ix);
+    if (!d_len || !dmin || !span) throw sme::Error(SME_EINVAL, "null argument");
+    set_device(ix->ctx);
+    sme::prepare_bm25(ix, stream_of(ix->ctx, stream));
+    *d_len = (const int32_t *)ix->d_bm_dl.p;
+    *dmin = ix->dmin;
+    *span = ix->bm_span;
+  });
+}
+
+int sme_index_bm25_stats(const sme_index *ix, uint64_t *docs, uint64_t *total_len, uint64_t *max_len, uint64_t *window) {
+  return guard([&] {
+    need_bm25_index(ix);
+    if (!docs || !total_len || !max_len || !window) throw sme::Error(SME_EINVAL, "null argument");
+    set_device(ix->ctx);
+    sme::prepare_bm25(const_cast<sme_index *>(ix), ix->ctx->own_stream);  // (the tables are a cache of the postings)
+    *docs = ix->bm_docs;
+    *total_len = ix->bm_total_len;
+    *max_len = ix->bm_max_len;
+    *window = (uint64_t)sme::bm25::kWindow;
+  });
+}
+
+// the checks of a BM25 call that need no device; offs: the offsets on the host
+static void need_bm25_args(const sme_index *ix, const int32_t *ids, const int64_t *offs, int nq, int k, double k1,
+                           double b) {
+  if (nq < 0) throw sme::Error(SME_EINVAL, "bm25: nq must be >= 0");
+  if (k < 1) throw sme::Error(SME_EINVAL, "bm25: k must be >= 1");
+  if (!sme::bm25::legal_params(k1, b))
+    throw sme::Error(SME_EINVAL, "bm25: k1 must be finite and >= 0, b in [0, 1]");
+  if (k > sme::bm25::kMaxK) throw sme::Error(SME_ELIMIT, "bm25: k > " + std::to_string(sme::bm25::kMaxK));
+  int bad = -1;
+  const int rc = sme::bm25::validate(ids, -1, offs, nq, ix->V, &bad);
+  const std::string at = bad >= 0 ? " (query " + std::to_string(bad) + ")" : "";
+  if (rc == sme::bm25::M_OFFSETS) throw sme::Error(SME_EINVAL, "bm25: q_offsets do not ascend from 0" + at);
+  if (rc == sme::bm25::M_SLOTS)
+    throw sme::Error(SME_ELIMIT, "bm25: more than " + std::to_string(sme::bm25::kMaxSlots) + " term slots" + at);
+  if (rc == sme::bm25::M_TERM) throw sme::Error(SME_EINVAL, "bm25: a term id outside [-1, V)" + at);
+}
+
+int sme_query_topk_bm25_device(sme_index *ix, const int32_t *d_term_ids, const int64_t *d_q_offsets, int nq, int k,
+                               double k1, double b, int32_t *d_out_docno, double *d_out_score, void *stream) {
+  return guard([&] {
+    need_bm25_index(ix);
+    if (nq > 0 && (!d_term_ids || !d_q_offsets || !d_out_docno || !d_out_score))
+      throw sme::Error(SME_EINVAL, "null argument");
+    set_device(ix->ctx);
+    hipStream_t st = stream_of(ix->ctx, stream);
+    // the offsets come to the host: the slot limit is checked before a launch, the ids
+    // by the scorer (an id outside [0, V) is skipped like -1)
+    std::vector<int64_t> offs((size_t)std::max(nq, 0) + 1, 0);
+    if (nq > 0) {
+      SME_HIP(hipMemcpyAsync(offs.data(), d_q_offsets, offs.size() * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+      SME_HIP(hipStreamSynchronize(st));
+    }
+    need_bm25_args(ix, nullptr, offs.data(), nq, k, k1, b);
+    sme::query_topk_bm25(ix, d_term_ids, d_q_offsets, offs.data(), nq, k, k1, b, d_out_docno, d_out_score, st);
+  });
+}
+
+int sme_query_topk_bm25(sme_index *ix, const int32_t *term_ids, const int64_t *q_offsets, int nq, int k, double k1,
+                        double b, int32_t *out_docno, double *out_score) {
+  return guard([&] {
+    need_bm25_index(ix);
+    if (nq > 0 && (!term_ids || !q_offsets || !out_docno || !out_score)) throw sme::Error(SME_EINVAL, "null argument");
+    need_bm25_args(ix, term_ids, q_offsets, nq, k, k1, b);
+    set_device(ix->ctx);
+    hipStream_t st = ix->ctx->own_stream;
+    const int64_t nt = nq > 0 ? q_offsets[nq] : 0;
+    sme::DevBuf a, c, d, e;
+    int32_t *dt = a.as<int32_t>((size_t)nt + 1);
+    int64_t *dq = c.as<int64_t>((size_t)nq + 1);
+    int32_t *dd = d.as<int32_t>((size_t)nq * k);
+    double *ds = e.as<double>((size_t)nq * k);
+    if (nt) SME_HIP(hipMemcpyAsync(dt, term_ids, (size_t)nt * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    if (nq > 0) SME_HIP(hipMemcpyAsync(dq, q_offsets, ((size_t)nq + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    sme::query_topk_bm25(ix, dt, dq, q_offsets, nq, k, k1, b, dd, ds, st);
+    if (nq > 0) {
+      SME_HIP(hipMemcpyAsync(out_docno, dd, (size_t)nq * k * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+      SME_HIP(hipMemcpyAsync(out_score, ds, (size_t)nq * k * sizeof(double), hipMemcpyDeviceToHost, st));
+    }
+    SME_HIP(hipStreamSynchronize(st));
+  });
+}
+
+int sme_query_bm25_stats(const sme_index *ix, uint64_t *windows, uint64_t *skipped, uint64_t *postings) {
+  return guard([&] {
+    if (!ix || !windows || !skipped || !postings) throw sme::Error(SME_EINVAL, "null argument");
+    unsigned long long h[3] = {0, 0, 0};
+    if (ix->bm_called) {
+      set_device(ix->ctx);
+      SME_HIP(hipMemcpyAsync(h, ix->d_bm_stat.p, sizeof h, hipMemcpyDeviceToHost, ix->bm_stream));
+      SME_HIP(hipStreamSynchronize(ix->bm_stream));
+    }
+    *windows = h[0];
+    *skipped = h[1];
+    *postings = h[2];
+  });
 }
 
 int sme_index_term_fingerprints(sme_index *ix, uint64_t *d_out, void *stream) {

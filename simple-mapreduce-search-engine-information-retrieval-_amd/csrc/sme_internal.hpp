@@ -79,6 +79,7 @@ struct sme_ctx {
   int64_t opt_fb_slots = 4096;    // "fb_slots": entries of relevance feedback's on-chip table (16..4096, a power of two)
   int64_t opt_merge_tile = 1024;  // "merge_tile": postings per tile of the index merger (64..2048, multiples of 64)
   int64_t opt_merge_append = 1;   // "merge_append": 1 = inputs of disjoint docno ranges are laid end to end, 0 = always merged
+  int64_t opt_bm25_split = 0;     // "bm25_split": BM25 scorer workgroups per query (0 = auto; capped at the window count)
   int64_t opt_delete_tile = 16384; // "delete_tile": postings per tile of the index deletion pass (256..65536, multiples of 256)
   int64_t opt_corpus_keep = int64_t(16) << 30;  // "corpus_keep_bytes": host-corpus builds keep their device copy
                                                 // (no hipMalloc next build) only up to this size
@@ -225,6 +226,19 @@ struct sme_index {
   std::vector<uint8_t> h_pf_file;
   uint64_t pf_bytes = 0, pf_bits = 0, pf_checked = 0;
   float pf_encode_ms = 0.0f, pf_decode_ms = 0.0f, pf_crosscheck_ms = 0.0f;
+  // BM25 ranking (sme_bm25.hip): the collection tables, built once per index (they
+  // depend on the postings only), the last call's norm table and its counts
+  sme::DevBuf d_bm_dl;     // int32 [bm_span]   dl[docno - dmin], 0 for a docno without postings
+  sme::DevBuf d_bm_idf;    // double [V]        host-libm idf by true df
+  sme::DevBuf d_bm_maxtf;  // int32 [V]         largest tf of every term
+  sme::DevBuf d_bm_mindl;  // int32 [bm_nwin]   smallest non-zero dl of every window
+  sme::DevBuf d_bm_norm;   // double [bm_span]  the last call's norm_d
+  sme::DevBuf d_bm_stat;   // u64 [3]           the last call's windows, skipped, postings
+  int64_t bm_span = 0, bm_nwin = 0;
+  uint64_t bm_docs = 0, bm_total_len = 0, bm_max_len = 0;
+  bool bm_ready = false, bm_called = false;
+  float bm_ms = 0.0f;
+  hipStream_t bm_stream = nullptr;  // the last call's stream (the counts are read behind it)
   // stage timings of the build that produced this index (ms)
   std::vector<std::pair<std::string, float>> profile;
   ~sme_index() { ctx->live_indexes--; }  // members (pooled buffers) are released after this body
@@ -233,7 +247,8 @@ struct sme_index {
     for (sme::DevBuf *b : {&d_term_off, &d_term_chars, &d_off, &d_docno_d, &d_tf_d, &d_w, &d_idf, &d_lut, &d_gram, &d_docno_o,
                            &d_tf_o, &d_rec_docno, &d_rec_first, &d_ser, &d_hrow_of, &d_heavy, &d_spk, &d_wkeys, &d_wgoff,
                            &d_wgterm, &d_wx_in, &d_wx_plan, &d_wx_choff, &d_wx_moff, &d_wx_scan, &d_ps_off, &d_ps_terms,
-                           &d_ps_docno, &d_nq_lut, &d_pf_file})
+                           &d_ps_docno, &d_nq_lut, &d_pf_file, &d_bm_dl, &d_bm_idf, &d_bm_maxtf, &d_bm_mindl, &d_bm_norm,
+                           &d_bm_stat})
       b->pool = &c->pool;
     for (sme::ResultSet *r : std::initializer_list<sme::ResultSet *>{&wx, &fz, &bq, &pq, &nq, &sq, &sv, &fb})
       r->bind(&c->pool);
@@ -515,6 +530,13 @@ void feedback_terms(sme_index *ix, const int32_t *docnos, bool on_device, const 
 void query_structured(sme_index *ix, const int32_t *term_ids, const int64_t *l_offsets, const uint8_t *l_kinds,
                       const int32_t *l_widths, const int64_t *g_offsets, const uint8_t *g_flags,
                       const int64_t *q_offsets, int nq, int order, int m, hipStream_t st);
+// BM25 ranking (sme_bm25.hip): the index's collection tables (document lengths, idf
+// by true df, the bound tables), built once; and nq queries of term ids in device
+// memory -> per query the k best documents by BM25 score, laid out as query_topk's.
+// h_qoff: the offsets' host copy, validated by the caller.
+void prepare_bm25(sme_index *ix, hipStream_t st);
+void query_topk_bm25(sme_index *ix, const int32_t *d_terms, const int64_t *d_qoff, const int64_t *h_qoff, int nq, int k,
+                     double k1, double b, int32_t *d_out_docno, double *d_out_score, hipStream_t st);
 // The idf of a term with document frequency df among N documents, the one
 // expression behind the build's idf tables (idf_by_df[df] = idf_value(N, df),
 // idf_by_q[q] = idf_value(q, 1) read at q = N / df: log10 of the integer quotient)
