@@ -24,7 +24,10 @@
 // arrays; k_rs_term_off reads the terms' first slots out of that pass's offset
 // table, so no pass over the sorted keys is needed for the CSR offsets.  After
 // the single-pass aggregation the first pass gathers its items from the
-// records' regions, one packed word per pair (Gather).
+// records' regions, one packed word per pair (Gather): each wave builds a mask
+// of the record starts among its 1024 items and a table of those records, in
+// LDS that the scatter stages through later, and forms every item's address
+// from a bit count and one table read, none waiting for the item before it.
 #include <hip/hip_runtime.h>
 
 #include "sme_internal.hpp"
@@ -63,23 +66,22 @@ static RsGroups rs_groups(int64_t ntiles) {
 // Gather mode (first pass after the single-pass aggregation): pair x of the
 // docno order lives in the region of the record i holding it,
 // reg[i] + (x - xoff[i]) (xoff = exclusive scan of the records' pair counts);
-// crec[c] = the record holding pair 1024 c, so a wave's walk over its 1024
-// items starts there and advances a record at a time.
+// crec[c] = the record holding pair 1024 c, the first record of the wave whose
+// 1024 items start there.
 // Packed form (rval != nullptr): the region holds one word per pair,
 // term | tf << tf_shift, and rval[i] = (docno - dmin) * F of record i, so the
 // pair's key is the word's low tf_shift bits and its value rval[i] + tf; no
 // value array is read.
+// No item's address depends on the item before it (gather_addr): the wave keeps
+// a 1024-bit mask of the record starts among its items and a table of the
+// records that own them, and an item finds its record by counting mask bits.
 struct Gather {
   const int64_t *reg, *xoff, *crec;
   int64_t nrec;
   const uint32_t *rval;
   int tf_shift;
 };
-__device__ __forceinline__ void gather_start(const Gather &g, int64_t x, int64_t &rec, int64_t &nx, int64_t &dl) {
-  rec = g.crec[x >> 10];
-  nx = g.xoff[rec + 1];
-  dl = g.reg[rec] - g.xoff[rec];
-}
+// the global walk: the items a wave's table does not cover (gather_addr)
 __device__ __forceinline__ int64_t gather_pos(const Gather &g, int64_t x, int64_t &rec, int64_t &nx, int64_t &dl) {
   while (x >= nx) {
     rec++;
@@ -88,43 +90,109 @@ __device__ __forceinline__ int64_t gather_pos(const Gather &g, int64_t x, int64_
   }
   return x + dl;
 }
-// A wave's 1024 items span a few records: lane j loads record rec0 + j's pair
-// start and region delta into LDS once, so the per-item walk reads LDS and the
-// item loads are not held behind dependent global loads (vmcnt is in order).
-// Walks past kGRec records fall back to the global walk.  gv (packed form): the
-// records' base values, a third column of the table; gather_at then also gives
-// the item's record, as its distance jr from the wave's first (the base value is
-// looked up once every item load is issued: gv[jr], or rval past the table).
-constexpr int kGRec = 48;  // (LDS: two 512-thread scatter blocks per CU)
-__device__ __forceinline__ int64_t gather_table(const Gather &g, int64_t x0, int lane, int64_t *gx, int64_t *gdl,
-                                                uint32_t *gv = nullptr) {
-  const int64_t rec0 = g.crec[x0 >> 10];
-  const int64_t r = rec0 + lane;
-  if (lane < kGRec) {
-    gx[lane] = r <= g.nrec ? g.xoff[r] : INT64_MAX;
-    gdl[lane] = r < g.nrec ? g.reg[r] - g.xoff[r] : 0;
-    if (gv) gv[lane] = r < g.nrec ? g.rval[r] : 0u;
-  }
-  if (lane == 0) gx[kGRec] = rec0 + kGRec <= g.nrec ? g.xoff[rec0 + kGRec] : INT64_MAX;
+// One wave's table.  m: bit b is set when pair x0 + b (x0 = the wave's first
+// item, b >= 1) is the first pair of a record; records without pairs set no bit.
+// Slot 0 is the record holding pair x0 (crec), whether it starts there or
+// before; slot q >= 1 is the record of the q-th set bit.  dl[q] = reg - xoff of
+// slot q's record (region deltas are kept as int64: no narrower form, so no
+// range check), bv[q] its base value (packed form).  An item at bit b is in slot
+// popcount(m & bits 0..b).
+constexpr int kGScan = 256;  // records from the wave's first on that one table covers (64 per round): its slots
+struct __attribute__((may_alias)) GatherTab {
+  unsigned long long m[kRsIPL];
+  int64_t dl[kGScan];
+  uint32_t bv[kGScan];
+};
+__device__ __forceinline__ int64_t wave_lane_i64(int64_t v, int src) {  // lane src's v, wave-uniform
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, src);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)((uint64_t)v >> 32), src);
+  return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+// gather_fill builds the table of the wave whose items are [x0, x0 + 1024) (x0 a
+// multiple of 1024 below P).  The lanes read 64 records a round from the wave's
+// first on, each its own with independent loads (two memory round trips a wave:
+// crec, then these), until the records read reach the wave's end or kGScan
+// of them are read; a record with pairs that starts inside the wave takes the
+// next slot (a ballot count: no lane waits for another) and sets its bit.  Items
+// at or past xlim = the first pair of the first record not read (a wave cut into
+// more than kGScan records, runs of empty ones included) are not covered.
+struct GatherWave {
+  int64_t rend, xlim;  // records [crec, rend) are in the table; xlim = xoff[rend], INT64_MAX past the last record
+};
+__device__ __forceinline__ GatherWave gather_fill(const Gather &g, int64_t x0, int lane, GatherTab *t, bool bq) {
+  const int64_t rec0 = g.crec[x0 >> 10], xend = x0 + kRsWaveItems;
+  const uint64_t lt = (1ull << lane) - 1ull;
+  if (lane < kRsIPL) t->m[lane] = 0ull;
   __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
   __builtin_amdgcn_wave_barrier();
-  return rec0;
+  int64_t rend = rec0, xlim;
+  int nq = 1;
+  do {
+    // (every load at a clamped, valid index: none waits for a branch or for another)
+    const int64_t r = rend + lane, rc = min(r, g.nrec - 1);
+    const bool in = r < g.nrec;
+    const int64_t xs = g.xoff[rc], xn = g.xoff[rc + 1], rg = g.reg[rc];
+    const uint32_t b = bq ? g.rval[rc] : 0u;
+    const int64_t xe = in ? xn : INT64_MAX;
+    // rec0 holds pair x0, so it is slot 0 and sets no bit, and every later record starts past x0
+    const bool own = in && xn > xs && xs > x0 && xs < xend;
+    const uint64_t ob = (uint64_t)__ballot(own);
+    if (own || r == rec0) {
+      const int q = own ? nq + (int)__popcll(ob & lt) : 0;
+      t->dl[q] = rg - xs;
+      if (bq) t->bv[q] = b;
+      if (own) atomicOr(&t->m[(xs - x0) >> 6], 1ull << ((xs - x0) & 63));
+    }
+    nq += (int)__popcll(ob);
+    rend += 64;
+    xlim = wave_lane_i64(xe, 63);
+  } while (xlim < xend && rend - rec0 < kGScan);
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  return GatherWave{rend, xlim};
 }
-__device__ __forceinline__ int64_t gather_at(const Gather &g, int64_t x, int &j, const int64_t *gx, const int64_t *gdl,
-                                             int64_t rec0, uint32_t *jr = nullptr) {
-#ifdef SME_RS_GATHER_CEIL  // (experiment, timing only: no walk.  Right only where the regions are one dense run)
-  if (jr) *jr = 0u;
-  return x + gdl[0];
-#endif
-  while (j < kGRec - 1 && x >= gx[j + 1]) j++;
-  if (x < gx[j + 1]) {
-    if (jr) *jr = (uint32_t)j;
-    return x + gdl[j];
+// Source addresses a[s - S0] of the wave's items x0 + 64 s + lane, s in
+// [S0, S0 + NS) (entries of items >= P are not to be used).  An item's slot is
+// a popcount over wave-uniform mask words and its address one LDS read away, so
+// the items of a lane are independent of each other.  Items the table does not
+// cover take the global walk from its end: correct for any input, slow only
+// there.  A slot index is at most the number of owning records read, so it
+// stays inside the table whatever the input.
+// bq (packed form): bq[s - S0] = the item's slot, its base value bv[slot] to be
+// read once the item loads are issued; for a walked item the base value itself,
+// with bit s of the result set.
+template <int S0, int NS>
+__device__ __forceinline__ uint32_t gather_addr(const Gather &g, int64_t x0, int64_t P, int lane, const GatherTab *t,
+                                                const GatherWave &gw, int64_t (&a)[NS], uint32_t *bq) {
+  const int64_t mv = (int64_t)t->m[lane & (kRsIPL - 1)];
+  const uint64_t le = ((1ull << lane) - 1ull) | (1ull << lane);
+  int pre = 0;
+#pragma unroll
+  for (int s = 0; s < S0 + NS; s++) {
+    const uint64_t mw = (uint64_t)wave_lane_i64(mv, s);
+    if (s >= S0) {
+      const int q = pre + (int)__popcll(mw & le);
+      a[s - S0] = x0 + s * 64 + lane + t->dl[q];
+      if (bq) bq[s - S0] = (uint32_t)q;
+    }
+    pre += (int)__popcll(mw);
   }
-  int64_t rec = rec0 + kGRec - 1, nx = g.xoff[rec + 1], dl = g.reg[rec] - g.xoff[rec];
-  const int64_t p = gather_pos(g, x, rec, nx, dl);
-  if (jr) *jr = (uint32_t)(rec - rec0);
-  return p;
+  uint32_t walked = 0u;
+  if (gw.xlim < min(x0 + kRsWaveItems, P)) {
+#pragma unroll
+    for (int s = S0; s < S0 + NS; s++) {
+      const int64_t x = x0 + s * 64 + lane;
+      if (x >= gw.xlim && x < P) {
+        int64_t rec = gw.rend - 1, nx = gw.xlim, dl = 0;
+        a[s - S0] = gather_pos(g, x, rec, nx, dl);
+        if (bq) {
+          bq[s - S0] = g.rval[rec];
+          walked |= 1u << s;
+        }
+      }
+    }
+  }
+  return walked;
 }
 __global__ void k_rs_chunk_rec(const int64_t *__restrict__ xoff, int64_t nrec, int64_t P, int64_t *__restrict__ crec) {
   for (int64_t c = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; (c << 10) < P; c += (int64_t)gridDim.x * blockDim.x) {
@@ -149,18 +217,20 @@ __global__ __launch_bounds__(kRsNT) void k_rs_count(const uint32_t *__restrict__
   const uint32_t mask = (uint32_t)nbins - 1u;
   const int64_t n = min((int64_t)kRsTile, P - t0);
   if (g.reg != nullptr) {
-    __shared__ int64_t gx_all[kRsWaves][kGRec + 1], gdl_all[kRsWaves][kGRec];
+    __shared__ GatherTab gt_all[kRsWaves];
     const int lane = tid & 63, w = tid >> 6;
     const int64_t wb = t0 + (int64_t)w * kRsWaveItems;
     if (wb < P) {
-      const int64_t rec0 = gather_table(g, wb, lane, gx_all[w], gdl_all[w]);
-      int j = 0;
+      const GatherWave gw = gather_fill(g, wb, lane, &gt_all[w], false);
       uint32_t kk[kRsIPL];
+      constexpr int kH = kRsIPL / 2;  // (the addresses a half at a time: registers)
+      int64_t a[kH];
+      gather_addr<0, kH>(g, wb, P, lane, &gt_all[w], gw, a, nullptr);
 #pragma unroll
-      for (int s = 0; s < kRsIPL; s++) {
-        const int64_t x = wb + s * 64 + lane;
-        kk[s] = x < P ? key[gather_at(g, x, j, gx_all[w], gdl_all[w], rec0)] : 0u;
-      }
+      for (int s = 0; s < kH; s++) kk[s] = wb + s * 64 + lane < P ? key[a[s]] : 0u;
+      gather_addr<kH, kH>(g, wb, P, lane, &gt_all[w], gw, a, nullptr);
+#pragma unroll
+      for (int s = kH; s < kRsIPL; s++) kk[s] = wb + s * 64 + lane < P ? key[a[s - kH]] : 0u;
 #pragma unroll
       for (int s = 0; s < kRsIPL; s++)
         if (wb + s * 64 + lane < P) atomicAdd(&h[(kk[s] >> shift) & mask], 1u);
@@ -281,7 +351,7 @@ __global__ __launch_bounds__(kRsNT) void k_rs_scatter(const uint32_t *__restrict
   // the tile sorted by digit; gd: global offset - tile slot of each digit
   __shared__ uint16_t wc[kRsWaves * kRsMaxBins];
   __shared__ uint32_t gd[kRsMaxBins];
-  __shared__ uint32_t stage[kRsTile];
+  __shared__ __align__(16) uint32_t stage[kRsTile];  // (first the gather tables, see below)
   __shared__ uint32_t ws[kRsWaves];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int nbins = 1 << nbits;
@@ -303,40 +373,40 @@ __global__ __launch_bounds__(kRsNT) void k_rs_scatter(const uint32_t *__restrict
   const uint64_t lt = (1ull << lane) - 1ull;
   uint32_t k[kRsIPL], v[kRsIPL], pos[kRsIPL];
   if (g.reg != nullptr) {
-    __shared__ int64_t gx_all[kRsWaves][kGRec + 1], gdl_all[kRsWaves][kGRec];
-    __shared__ uint32_t gv_all[kRsWaves][kGRec];
-    uint32_t *gv = PACK ? gv_all[w] : nullptr;
-    int64_t rec0 = 0;
-    if (wb < n) rec0 = gather_table(g, t0 + wb, lane, gx_all[w], gdl_all[w], gv);
-    int j = 0;
+    // The wave's gather table lives in stage: every read of it is done before the
+    // barrier that ends step 1, and stage is first written in step 3.
+    static_assert(kRsWaves * sizeof(GatherTab) <= sizeof(stage), "the gather tables alias stage");
+    GatherTab *gt = reinterpret_cast<GatherTab *>(stage) + w;
+    int64_t a[kRsIPL];
+#pragma unroll
+    for (int s = 0; s < kRsIPL; s++) {
+      a[s] = 0;
+      k[s] = 0u;
+      v[s] = 0u;
+    }
     if (PACK) {  // packed words: key = low tf_shift bits, value = the record's base + tf
       const uint32_t kmask = g.tf_shift >= 32 ? 0xFFFFFFFFu : (1u << g.tf_shift) - 1u;
+      uint32_t walked = 0u;
+      if (wb < n) walked = gather_addr<0, kRsIPL>(g, t0 + wb, P, lane, gt, gather_fill(g, t0 + wb, lane, gt, true), a, v);
 #pragma unroll
-      for (int s = 0; s < kRsIPL; s++) {
-        const int i = wb + s * 64 + lane;
-        k[s] = 0u;
-        v[s] = 0u;
-        if (i < n) k[s] = key[gather_at(g, t0 + i, j, gx_all[w], gdl_all[w], rec0, &v[s])];
-      }
+      for (int s = 0; s < kRsIPL; s++)
+        if (wb + s * 64 + lane < n) k[s] = key[a[s]];
       // (unpacked after the loop: a use of the word inside the branch above would
       // make every load wait for the one before it)
 #pragma unroll
       for (int s = 0; s < kRsIPL; s++) {
-        const uint32_t wd = k[s], jr = v[s];
+        const uint32_t wd = k[s], q = v[s];
         k[s] = wd & kmask;
         if (wb + s * 64 + lane < n)
-          v[s] = (jr < (uint32_t)kGRec ? gv[jr] : g.rval[rec0 + jr]) + (uint32_t)((uint64_t)wd >> g.tf_shift);
+          v[s] = ((walked >> s) & 1u ? q : gt->bv[q]) + (uint32_t)((uint64_t)wd >> g.tf_shift);
       }
     } else {
+      if (wb < n) gather_addr<0, kRsIPL>(g, t0 + wb, P, lane, gt, gather_fill(g, t0 + wb, lane, gt, false), a, nullptr);
 #pragma unroll
       for (int s = 0; s < kRsIPL; s++) {
-        const int i = wb + s * 64 + lane;
-        k[s] = 0u;
-        v[s] = 0u;
-        if (i < n) {
-          const int64_t p = gather_at(g, t0 + i, j, gx_all[w], gdl_all[w], rec0);
-          k[s] = key[p];
-          v[s] = val[p];
+        if (wb + s * 64 + lane < n) {
+          k[s] = key[a[s]];
+          v[s] = val[a[s]];
         }
       }
     }
