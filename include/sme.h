@@ -172,6 +172,9 @@ void sme_destroy(sme_ctx *ctx);
  *                   Results are the same
  *   "bm25_split"    sme_query_topk_bm25*: scorer workgroups per query, 0 (default) automatic,
  *                   >= 1 that many (capped at the window count and at 4096).  Results are the same
+ *   "rescore_path"  sme_query_rescore*: how a term slot meets a tile of candidates, 0 (default)
+ *                   the cheaper form by the two lengths, 1 always a search of the term's list
+ *                   per candidate, 2 always a scan of the list against the tile.  Results are the same
  * Unknown names and out-of-range values are SME_EINVAL. */
 int sme_set_option(sme_ctx *ctx, const char *name, int64_t value);
 
@@ -816,6 +819,70 @@ int sme_query_topk_bm25(sme_index *ix, const int32_t *term_ids, const int64_t *q
 int sme_query_topk_bm25_device(sme_index *ix, const int32_t *d_term_ids, const int64_t *d_q_offsets, int nq, int k,
                                double k1, double b, int32_t *d_out_docno, double *d_out_score, void *stream);
 int sme_query_bm25_stats(const sme_index *ix, uint64_t *windows, uint64_t *skipped, uint64_t *postings);
+
+/* Scoring given documents: per query a list of term slots and a list of docnos ->
+ * every listed document's score under TF-IDF or BM25.  What ranks the result of a
+ * Boolean, phrase, proximity or structured query under either model, ranks "only
+ * these documents" of a filter kept outside the index, and re-ranks one stage's
+ * candidates with other parameters without another pass over the collection.  For
+ * an index with a query side (a records-only merged index and a chargram output are
+ * SME_EINVAL).
+ *
+ * Inputs.  Query i has the term slots term_ids[q_offsets[i] .. q_offsets[i+1]) --
+ * host arrays in both entries, as in the other batched features -- and the
+ * candidates docnos[d_offsets[i] .. d_offsets[i+1]), nq + 1 offsets from 0.  A
+ * query's candidates are STRICTLY ASCENDING in signed int32 order: exactly what
+ * order 0 of sme_query_boolean / _phrase / _near / _structured returns.  In the device
+ * entry both candidate arrays are device memory, so the d_res_off / d_docno of
+ * another feature's device call go in unchanged; the entry copies the nq + 1 offsets
+ * to the host to check them (one synchronisation, as sme_query_topk_bm25_device
+ * does) and a kernel checks the ascending rule before any score is written.
+ *
+ * model 0, TF-IDF: a document's score is the fp64 sum from 0.0, over the slots in
+ * listed order, of the weight at the document's posting in the slot's list: a slot
+ * whose list lacks the document adds nothing, a term listed twice counts twice, -1
+ * slots are skipped.  Weights are read at call time (sme_index_reweight).  This is
+ * the sum sme_query_boolean documents, and its bits are those sme_query_topk gives
+ * that document for that term list.  k1 and b are not read.
+ * model 1, BM25: exactly sme_query_topk_bm25's w(t, d) above, summed the same way,
+ * from the tables of sme_index_prepare_bm25 (built on first use), under the same rule
+ * for k1 and b.  The call leaves the last BM25 call's result and counts alone.
+ *
+ * Results.  hits = the slots, duplicates counted, whose list holds the document.
+ * Every candidate with hits >= min_hits is a match: min_hits 0 keeps documents the
+ * index has never seen (hits 0, score 0.0), min_hits 1 is "holds at least one term".
+ * A candidate outside the index's docno range, or without a posting, is legal.
+ * order 0: the matches in the given (docno) order; no sort runs on this path.
+ * order 1: score descending, then docno ascending.  Both are then cut to the first m;
+ * m == 0: no cut.  Query i's matches are docno / hits / score [res_off[i],
+ * res_off[i+1]).  The arrays (host memory from the host entry, device memory from the
+ * device entry) are owned by the index until its next rescore call; every other
+ * feature's buffers are left alone, and no other feature touches these.
+ *
+ * SME_EINVAL (the message names the query where there is one): candidates not
+ * strictly ascending -- the index's rescore result is then empty --, offsets of
+ * either kind not ascending from 0, a term id outside [-1, V), a model or an order
+ * other than 0 / 1, m < 0, min_hits < 0, nq < 0, illegal k1 / b under model 1.
+ * SME_ELIMIT: more than 1024 slots in a query; 2^31 or more candidates, or slots, in
+ * a batch.  nq == 0, a query without candidates and a query without slots are valid.
+ *
+ * One workgroup scores one tile of 1024 consecutive candidates of a query
+ * (sme_query_rescore_stats's *tile).  Per slot it narrows the term's list to the
+ * tile's docno range and then either scans that range against the tile or searches
+ * it for every candidate.  Option "rescore_path": 0 (default) the cheaper form by the
+ * two lengths, 1 always search, 2 always scan.  Results are the same for every value.
+ *
+ * sme_query_rescore_stats reports on the last rescore call: the batch's candidates,
+ * the sum of hits, the matches before the cut, and the tile size. */
+int sme_query_rescore(sme_index *ix, const int32_t *term_ids, const int64_t *q_offsets, const int32_t *docnos,
+                      const int64_t *d_offsets, int nq, int model, double k1, double b, int min_hits, int order, int m,
+                      const int64_t **res_off, const int32_t **docno, const int32_t **hits, const double **score);
+int sme_query_rescore_device(sme_index *ix, const int32_t *term_ids, const int64_t *q_offsets, const int32_t *d_docnos,
+                             const int64_t *d_doc_offsets, int nq, int model, double k1, double b, int min_hits,
+                             int order, int m, void *stream, const int64_t **d_res_off, const int32_t **d_docno,
+                             const int32_t **d_hits, const double **d_score, int64_t *total);
+int sme_query_rescore_stats(const sme_index *ix, uint64_t *candidates, uint64_t *found, uint64_t *matches,
+                            uint64_t *tile);
 
 /* 128-bit fingerprint of every index term (two u64 per term into device memory
  * d_out[2 V]): equal term strings (k-grams) on different shards get equal

@@ -66,6 +66,7 @@ EXPORTS = [
     "sme_index_attach_positions_device", "sme_index_posfile_stats",
     "sme_index_prepare_bm25", "sme_index_doc_lengths", "sme_index_bm25_stats", "sme_query_topk_bm25",
     "sme_query_topk_bm25_device", "sme_query_bm25_stats",
+    "sme_query_rescore", "sme_query_rescore_device", "sme_query_rescore_stats",
 ]
 
 
@@ -197,6 +198,13 @@ def lib():
                                       C.POINTER(C.c_double)]
     L.sme_query_topk_bm25_device.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_double, C.c_double, vp, vp, vp]
     L.sme_query_bm25_stats.argtypes = [vp] + [C.POINTER(C.c_uint64)] * 3
+    L.sme_query_rescore.argtypes = [vp, i32p, i64p, i32p, i64p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int,
+                                    C.c_int, C.c_int, C.POINTER(i64p), C.POINTER(i32p), C.POINTER(i32p),
+                                    C.POINTER(f64p)]
+    L.sme_query_rescore_device.argtypes = [vp, i32p, i64p, vp, vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int,
+                                           C.c_int, C.c_int, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
+                                           C.POINTER(vp), i64p]
+    L.sme_query_rescore_stats.argtypes = [vp] + [C.POINTER(C.c_uint64)] * 4
     _lib = L
     return L
 
@@ -1121,6 +1129,55 @@ class Index:
         w, s, p = Index._stats(self._h, lib().sme_query_bm25_stats, 3)
         return {"windows": w, "skipped": s, "postings": p}
 
+    # ---- scoring given documents (include/sme.h, sme_query_rescore)
+    _MODELS = {"tfidf": 0, "bm25": 1, 0: 0, 1: 1}
+
+    @staticmethod
+    def _rescore_tail(model, k1, b, min_hits, order, m):
+        if model not in Index._MODELS:
+            raise ValueError("model must be \"tfidf\" or \"bm25\" (or 0 / 1), not %r" % (model,))
+        return [Index._MODELS[model], float(k1), float(b), int(min_hits), int(order), int(m)]
+
+    def rescore(self, term_ids, q_offsets, docnos, d_offsets, model="bm25", order=1, m=0, min_hits=0, k1=1.2,
+                b=0.75):
+        """sme_query_rescore: query i's term slots term_ids[q_offsets[i]:q_offsets[i+1]]
+        over its candidates docnos[d_offsets[i]:d_offsets[i+1]], strictly ascending --
+        what order 0 of query_boolean / _phrase / _near / _structured returns.  Every
+        candidate gets its score under `model` ("tfidf": the sum query_boolean
+        documents; "bm25": query_bm25's weights with k1, b) and hits, the slots whose
+        posting list holds it; those with hits >= min_hits are the matches, in the
+        given order (order 0) or by score descending then docno ascending (order
+        1), cut to the first m (0: no cut).  Returns (res_off int64[nq+1], docno
+        int32, hits int32, score float64) (include/sme.h)."""
+        a = [term_ids, q_offsets, docnos, d_offsets]
+        keep, ptrs = Index._typed_ptrs(a, (np.int32, np.int64, np.int32, np.int64))
+        nq = len(keep[1]) - 1
+        return Index._host_call(self._h, lib().sme_query_rescore,
+                                ptrs + [nq] + Index._rescore_tail(model, k1, b, min_hits, order, m), nq,
+                                Index._PASS_COLS)
+
+    def rescore_device(self, term_ids, q_offsets, d_docnos, d_doc_offsets, model="bm25", order=1, m=0, min_hits=0,
+                       k1=1.2, b=0.75, stream=None):
+        """sme_query_rescore_device: the candidates and their nq + 1 offsets in device
+        memory (pointers, or contiguous int32 / int64 device tensors) -- the docno
+        and res_off pointers of another feature's device call as they stand; the
+        term slots and their offsets are host arrays.  Returns (device pointer of
+        res_off int64[nq+1], of docno, hits int32[total], of score float64[total],
+        total); the arrays belong to the index until its next rescore call."""
+        keep, ptrs = Index._typed_ptrs([term_ids, q_offsets], (np.int32, np.int64))
+        nq = len(keep[1]) - 1
+        dev = [C.c_void_p((x.data_ptr() if hasattr(x, "data_ptr") else x) or 0) for x in (d_docnos, d_doc_offsets)]
+        return Index._device_call(self._h, lib().sme_query_rescore_device,
+                                  ptrs + dev + [nq] + Index._rescore_tail(model, k1, b, min_hits, order, m), stream,
+                                  Index._PASS_COLS)
+
+    def rescore_stats(self):
+        """The last rescore call: {"candidates": the batch's candidates, "found": the
+        sum of hits, "matches": the matches before the cut, "tile": candidates per
+        workgroup of the scorer}."""
+        c, f, mt, t = Index._stats(self._h, lib().sme_query_rescore_stats, 4)
+        return {"candidates": c, "found": f, "matches": mt, "tile": t}
+
     def reweight(self, n_global, d_df_global=None, stream=None):
         """TF-IDF weights with all-reduced N (and df) of a doc-sharded index."""
         _check(lib().sme_index_reweight(self._h, n_global, C.c_void_p(d_df_global or 0), C.c_void_p(stream or 0)))
@@ -1466,10 +1523,37 @@ class IntDocVectorsForwardIndex:
         self._groups = groups
         return groups
 
-    def rank_boolean(self, k=10):
-        """The first k documents (score desc, docno asc) matching get_boolean's groups."""
-        _, dn, _ = self.index.query_boolean([getattr(self, "_groups", [])], order=1, m=k)
-        return [int(d) for d in dn]
+    def _scorer(self, scorer):
+        """The scorer's name checked before a query runs for it."""
+        if scorer not in ("bm25", "tfidf"):
+            raise ValueError("scorer must be None, \"bm25\" or \"tfidf\", not %r" % (scorer,))
+        return scorer
+
+    def _rescored(self, device_result, slots, scorer, k, k1, b):
+        """The one query of a feature's order 0, m 0 device result (res_off, docno,
+        ..., total) ranked by `scorer` over `slots`: the first k docnos."""
+        slots = np.array(slots, np.int32)
+        off, dn = device_result[0], device_result[1]
+        r = self.index.rescore_device(slots, np.array([0, len(slots)], np.int64), dn, off, model=scorer, order=1, m=k,
+                                      min_hits=0, k1=k1, b=b)
+        total = r[4]
+        out = np.zeros(max(total, 1), np.int32)
+        if total:
+            _d2h(out, r[1], 4 * total)
+        return [int(d) for d in out[:total]]
+
+    def rank_boolean(self, k=10, scorer=None, k1=1.2, b=0.75):
+        """The first k documents (score desc, docno asc) matching get_boolean's groups.
+        scorer "bm25" or "tfidf": the matches ranked by that model over the required
+        groups' terms in listed order (Index.rescore_device over the device result;
+        k1, b: BM25's parameters); None: by the Boolean score."""
+        groups = getattr(self, "_groups", [])
+        if scorer is None:
+            _, dn, _ = self.index.query_boolean([groups], order=1, m=k)
+            return [int(d) for d in dn]
+        self._scorer(scorer)
+        slots = [int(t) for ids, excluded in groups if not excluded for t in ids]
+        return self._rescored(self.index.query_boolean_device([groups], order=0, m=0), slots, scorer, k, k1, b)
 
     def get_phrase(self, text):
         """An exact phrase from a text: processContent (stop words are dropped as
@@ -1481,10 +1565,16 @@ class IntDocVectorsForwardIndex:
         self._phrase = [int(t) for t in self.index.lookup(toks)] if toks else []
         return self._phrase
 
-    def rank_phrase(self, k=10):
-        """The first k documents (score desc, docno asc) holding get_phrase's phrase."""
-        _, dn, _, _ = self.index.query_phrase([getattr(self, "_phrase", [])], order=1, m=k)
-        return [int(d) for d in dn]
+    def rank_phrase(self, k=10, scorer=None, k1=1.2, b=0.75):
+        """The first k documents (score desc, docno asc) holding get_phrase's phrase.
+        scorer "bm25" or "tfidf": the matches ranked by that model over the phrase's
+        terms (Index.rescore_device); None: by the phrase score."""
+        phrase = getattr(self, "_phrase", [])
+        if scorer is None:
+            _, dn, _, _ = self.index.query_phrase([phrase], order=1, m=k)
+            return [int(d) for d in dn]
+        self._scorer(scorer)
+        return self._rescored(self.index.query_phrase_device([phrase], order=0, m=0), phrase, scorer, k, k1, b)
 
     def get_near(self, text, width, ordered=False):
         """A proximity query from a text: processContent -> the term lookup, as
@@ -1497,10 +1587,16 @@ class IntDocVectorsForwardIndex:
         self._near = (ids, int(width), bool(ordered))
         return self._near
 
-    def rank_near(self, k=10):
-        """The first k documents (score desc, docno asc) matching get_near's query."""
-        _, dn, _, _ = self.index.query_near([getattr(self, "_near", ([], 1, False))], order=1, m=k)
-        return [int(d) for d in dn]
+    def rank_near(self, k=10, scorer=None, k1=1.2, b=0.75):
+        """The first k documents (score desc, docno asc) matching get_near's query.
+        scorer "bm25" or "tfidf": the matches ranked by that model over the window's
+        terms (Index.rescore_device); None: by the proximity score."""
+        near = getattr(self, "_near", ([], 1, False))
+        if scorer is None:
+            _, dn, _, _ = self.index.query_near([near], order=1, m=k)
+            return [int(d) for d in dn]
+        self._scorer(scorer)
+        return self._rescored(self.index.query_near_device([near], order=0, m=0), near[0], scorer, k, k1, b)
 
     def get_similar(self, docno, terms=25):
         """More like this: the `terms` best feedback terms of the one document
@@ -1570,10 +1666,18 @@ class IntDocVectorsForwardIndex:
         self._structured = groups
         return groups
 
-    def rank_structured(self, k=10):
-        """The first k documents (score desc, docno asc) matching get_structured's query."""
-        _, dn, _ = self.index.query_structured([getattr(self, "_structured", [])], order=1, m=k)
-        return [int(d) for d in dn]
+    def rank_structured(self, k=10, scorer=None, k1=1.2, b=0.75):
+        """The first k documents (score desc, docno asc) matching get_structured's query.
+        scorer "bm25" or "tfidf": the matches ranked by that model over the term ids
+        of all leaves of the required groups, in listed order (Index.rescore_device);
+        None: by the structured score."""
+        groups = getattr(self, "_structured", [])
+        if scorer is None:
+            _, dn, _ = self.index.query_structured([groups], order=1, m=k)
+            return [int(d) for d in dn]
+        self._scorer(scorer)
+        slots = [int(t) for leaves, excluded in groups if not excluded for ids, _, _ in leaves for t in ids]
+        return self._rescored(self.index.query_structured_device([groups], order=0, m=0), slots, scorer, k, k1, b)
 
     def rank(self, k=10):
         if not self._terms:

@@ -12,6 +12,7 @@
 #include <thread>
 
 #include "sme_bm25.hpp"
+#include "sme_rescore.hpp"
 #include "sme_feedback.hpp"
 #include "sme_internal.hpp"
 #include "sme_ixmerge.hpp"
@@ -390,6 +391,9 @@ int sme_set_option(sme_ctx *cx, const char *name, int64_t v) {
     } else if (n == "bm25_split") {
       range(0, int64_t(1) << 30);
       cx->opt_bm25_split = v;
+    } else if (n == "rescore_path") {
+      range(sme::rescore::PATH_AUTO, sme::rescore::PATH_SCAN);
+      cx->opt_rescore_path = v;
     } else {
       throw sme::Error(SME_EINVAL, "unknown option " + n);
     }
@@ -1394,6 +1398,80 @@ int sme_query_bm25_stats(const sme_index *ix, uint64_t *windows, uint64_t *skipp
     *windows = h[0];
     *skipped = h[1];
     *postings = h[2];
+  });
+}
+
+// Scoring given documents runs over the query side of a TermKGramDocIndexer index.
+// The checks of a call that need no device; the batch itself is validated by
+// sme::rescore_docs.  term_ids / docnos may be NULL only in a batch without a slot /
+// a candidate (offs: the host copies of the offsets).
+static void need_rescore_index(const sme_index *ix) {
+  if (!ix) throw sme::Error(SME_EINVAL, "null index");
+  if (ix->job != 0) throw sme::Error(SME_EINVAL, "rescore: a CharKGramTermIndexer output has no postings by document");
+  if (ix->records_only)
+    throw sme::Error(SME_EINVAL, "rescore: records-only index (merged shard pieces): query the shard indexes");
+}
+static void need_rescore_args(const sme_index *ix, const int32_t *term_ids, const int64_t *q_offsets,
+                              const int32_t *docnos, const int64_t *d_offsets, int nq, int model, double k1, double b,
+                              int min_hits, int order, int m) {
+  need_rescore_index(ix);
+  if (nq < 0) throw sme::Error(SME_EINVAL, "rescore: nq must be >= 0");
+  if (nq > 0 && (!q_offsets || !d_offsets)) throw sme::Error(SME_EINVAL, "null argument");
+  if (!sme::rescore::legal_model(model)) throw sme::Error(SME_EINVAL, "rescore: model must be 0 (TF-IDF) or 1 (BM25)");
+  if (order != 0 && order != 1) throw sme::Error(SME_EINVAL, "rescore: order must be 0 (as given) or 1 (score)");
+  if (m < 0) throw sme::Error(SME_EINVAL, "rescore: m must be >= 0");
+  if (min_hits < 0) throw sme::Error(SME_EINVAL, "rescore: min_hits must be >= 0");
+  if (model == sme::rescore::MODEL_BM25 && !sme::bm25::legal_params(k1, b))
+    throw sme::Error(SME_EINVAL, "rescore: k1 must be finite and >= 0, b in [0, 1]");
+  // (offsets that do not start at 0 are refused by the validator before these arrays are read)
+  if (nq > 0 && q_offsets[0] == 0 && q_offsets[nq] > 0 && !term_ids) throw sme::Error(SME_EINVAL, "null argument");
+  if (nq > 0 && d_offsets[0] == 0 && d_offsets[nq] > 0 && !docnos) throw sme::Error(SME_EINVAL, "null argument");
+}
+
+int sme_query_rescore_device(sme_index *ix, const int32_t *term_ids, const int64_t *q_offsets, const int32_t *d_docnos,
+                             const int64_t *d_doc_offsets, int nq, int model, double k1, double b, int min_hits,
+                             int order, int m, void *stream, const int64_t **d_res_off, const int32_t **d_docno,
+                             const int32_t **d_hits, const double **d_score, int64_t *total) {
+  return guard([&] {
+    if (!d_res_off || !d_docno || !d_hits || !d_score) throw sme::Error(SME_EINVAL, "null argument");
+    need_rescore_index(ix);  // (before anything is copied for it)
+    if (nq > 0 && !d_doc_offsets) throw sme::Error(SME_EINVAL, "null argument");
+    set_device(ix->ctx);
+    hipStream_t st = stream_of(ix->ctx, stream);
+    // the candidates' offsets come to the host, where they are validated
+    std::vector<int64_t> offs((size_t)std::max(nq, 0) + 1, 0);
+    if (nq > 0) {
+      SME_HIP(hipMemcpyAsync(offs.data(), d_doc_offsets, offs.size() * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+      SME_HIP(hipStreamSynchronize(st));
+    }
+    // (a device array of candidates is not read here: any non-null value stands for it)
+    need_rescore_args(ix, term_ids, q_offsets, d_docnos, offs.data(), nq, model, k1, b, min_hits, order, m);
+    sme::rescore_docs(ix, term_ids, q_offsets, d_docnos, true, offs.data(), d_doc_offsets, nq, model, k1, b, min_hits,
+                      order, m, st);
+    device_arrays(ix->rs, d_res_off, d_docno, d_hits, d_score, total);
+  });
+}
+
+int sme_query_rescore(sme_index *ix, const int32_t *term_ids, const int64_t *q_offsets, const int32_t *docnos,
+                      const int64_t *d_offsets, int nq, int model, double k1, double b, int min_hits, int order, int m,
+                      const int64_t **res_off, const int32_t **docno, const int32_t **hits, const double **score) {
+  return guard([&] {
+    if (!res_off || !docno || !hits || !score) throw sme::Error(SME_EINVAL, "null argument");
+    need_rescore_args(ix, term_ids, q_offsets, docnos, d_offsets, nq, model, k1, b, min_hits, order, m);
+    set_device(ix->ctx);
+    hipStream_t st = ix->ctx->own_stream;
+    sme::rescore_docs(ix, term_ids, q_offsets, docnos, false, d_offsets, nullptr, nq, model, k1, b, min_hits, order, m,
+                      st);
+    host_arrays(ix->rs, st, res_off, docno, hits, score);
+  });
+}
+
+int sme_query_rescore_stats(const sme_index *ix, uint64_t *candidates, uint64_t *found, uint64_t *matches,
+                            uint64_t *tile) {
+  return guard([&] {
+    if (!ix || !candidates || !found || !matches || !tile) throw sme::Error(SME_EINVAL, "null argument");
+    pass_stats(ix->rs, candidates, found, matches);
+    *tile = (uint64_t)sme::rescore::kTile;
   });
 }
 

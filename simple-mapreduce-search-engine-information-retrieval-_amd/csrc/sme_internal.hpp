@@ -80,6 +80,7 @@ struct sme_ctx {
   int64_t opt_merge_tile = 1024;  // "merge_tile": postings per tile of the index merger (64..2048, multiples of 64)
   int64_t opt_merge_append = 1;   // "merge_append": 1 = inputs of disjoint docno ranges are laid end to end, 0 = always merged
   int64_t opt_bm25_split = 0;     // "bm25_split": BM25 scorer workgroups per query (0 = auto; capped at the window count)
+  int64_t opt_rescore_path = 0;   // "rescore_path": a rescore slot's form: 0 by its cost, 1 always search, 2 always scan
   int64_t opt_delete_tile = 16384; // "delete_tile": postings per tile of the index deletion pass (256..65536, multiples of 256)
   int64_t opt_corpus_keep = int64_t(16) << 30;  // "corpus_keep_bytes": host-corpus builds keep their device copy
                                                 // (no hipMalloc next build) only up to this size
@@ -239,6 +240,10 @@ struct sme_index {
   bool bm_ready = false, bm_called = false;
   float bm_ms = 0.0f;
   hipStream_t bm_stream = nullptr;  // the last call's stream (the counts are read behind it)
+  // scoring given documents (sme_rescore.hip): the last call's result (freq: the
+  // slots whose list holds the document; cands: the batch's candidates, verified:
+  // the sum of those hits)
+  sme::DocFreqScores rs;
   // stage timings of the build that produced this index (ms)
   std::vector<std::pair<std::string, float>> profile;
   ~sme_index() { ctx->live_indexes--; }  // members (pooled buffers) are released after this body
@@ -250,7 +255,7 @@ struct sme_index {
                            &d_ps_docno, &d_nq_lut, &d_pf_file, &d_bm_dl, &d_bm_idf, &d_bm_maxtf, &d_bm_mindl, &d_bm_norm,
                            &d_bm_stat})
       b->pool = &c->pool;
-    for (sme::ResultSet *r : std::initializer_list<sme::ResultSet *>{&wx, &fz, &bq, &pq, &nq, &sq, &sv, &fb})
+    for (sme::ResultSet *r : std::initializer_list<sme::ResultSet *>{&wx, &fz, &bq, &pq, &nq, &sq, &sv, &fb, &rs})
       r->bind(&c->pool);
   }
 };
@@ -537,6 +542,15 @@ void query_structured(sme_index *ix, const int32_t *term_ids, const int64_t *l_o
 void prepare_bm25(sme_index *ix, hipStream_t st);
 void query_topk_bm25(sme_index *ix, const int32_t *d_terms, const int64_t *d_qoff, const int64_t *h_qoff, int nq, int k,
                      double k1, double b, int32_t *d_out_docno, double *d_out_score, hipStream_t st);
+// scoring given documents (sme_rescore.hip): nq queries of term slots and strictly
+// ascending candidate docnos (the slots and both offset arrays: host arrays,
+// validated here; the candidates: device memory with their offsets' device copy if
+// on_device, where a kernel checks their order, else a host array) -> per query the
+// candidates with hits >= min_hits, their hits and scores (model 0 TF-IDF, 1 BM25),
+// ordered (0 as given, 1 score desc then docno asc) and cut to m: ix->rs
+void rescore_docs(sme_index *ix, const int32_t *term_ids, const int64_t *q_offsets, const int32_t *docnos,
+                  bool on_device, const int64_t *d_offsets, const int64_t *d_offsets_dev, int nq, int model, double k1,
+                  double b, int min_hits, int order, int m, hipStream_t st);
 // The idf of a term with document frequency df among N documents, the one
 // expression behind the build's idf tables (idf_by_df[df] = idf_value(N, df),
 // idf_by_q[q] = idf_value(q, 1) read at q = N / df: log10 of the integer quotient)
