@@ -884,6 +884,87 @@ int sme_query_rescore_device(sme_index *ix, const int32_t *term_ids, const int64
 int sme_query_rescore_stats(const sme_index *ix, uint64_t *candidates, uint64_t *found, uint64_t *matches,
                             uint64_t *tile);
 
+/* Best passages: where in a document the query matched.  Per query a list of term
+ * ids and a list of docnos -> for every listed document the best window of at most
+ * `width` consecutive positions of one of its records' term streams: what a result
+ * list shows as a snippet, highlights as hits, or returns as the best passage of a
+ * long document.  For a K = 1 index with a query side that keeps positions (built
+ * with option "positions" 1, or after sme_index_attach_positions); any other index
+ * is SME_EINVAL, and the message says which of the three it lacks.
+ *
+ * Inputs, as in sme_query_rescore.  Query i lists the term ids term_ids[q_offsets[i]
+ * .. q_offsets[i+1]) -- host arrays in both entries -- and the candidates
+ * docnos[d_offsets[i] .. d_offsets[i+1]), nq + 1 offsets from 0, STRICTLY ASCENDING
+ * per query in signed int32 order: what order 0 of sme_query_boolean / _phrase / _near
+ * / _structured returns.  In the device entry both candidate arrays are device
+ * memory; the entry copies the nq + 1 offsets to the host to check them and a kernel
+ * checks the ascending rule before anything is written.
+ *
+ * Slots.  Of a query's listed ids, -1 entries are dropped and a repeated id keeps its
+ * first place; the j-th distinct id in listed order is slot j, bit j of a row's mask.
+ * A query may list 1024 ids and hold 64 distinct ones.
+ *
+ * Windows.  The records of docno d are those of the index's term streams with that
+ * docno, in the index's record order (equal docnos stay in file order); their ordinal
+ * 0, 1, ... among the docno's records is rec.  A window never crosses a record's end:
+ * a record of n positions has the starts 0 .. max(0, n - width), and the window at
+ * start s is the positions [s, min(s + width, n)) -- an empty record has the one
+ * window (0, 0).  Of a window, mask is the OR of the slots of the positions whose term
+ * is a query term, cover the number of bits set in it, hits the number of such
+ * positions, and score the fp64 sum from 0.0, over the set bits of mask in ascending
+ * slot order, of the idf the index's weights use for the slot's term (additions only;
+ * read at call time, so sme_index_reweight is honoured).
+ * A candidate's best window is the first in the order: score descending, cover
+ * descending (which decides where an idf is 0.0), hits descending, rec ascending,
+ * start ascending.  A candidate without a record gets rec -1, start 0, len 0, mask 0,
+ * hits 0, score 0.0.
+ *
+ * Result A, the rows.  A candidate is kept when cover >= min_cover (0 keeps every
+ * candidate).  order 0: the kept candidates in the given (docno) order; no sort runs.
+ * order 1: score descending, then docno ascending.  Both are cut to the first m; m ==
+ * 0: no cut.  Query i's rows are [res_off[i], res_off[i+1]) of docno, rec, start, len,
+ * hits, mask and score; `total` is their number.
+ * Result B, the window terms, with with_terms 1: row r's window is [win_off[r],
+ * win_off[r+1]) of win_term, the stream's term ids at the window's positions, and
+ * win_slot, each position's slot or -1; win_off has total + 1 entries, the exclusive
+ * scan of the rows' len, and win_total is its last.  With with_terms 0 no kernel runs
+ * for it: win_off holds the one entry 0 and win_total is 0.
+ * Both results (host memory from the host entry, device memory from the device entry)
+ * are owned by the index until its next passages call; every other feature's buffers
+ * are left alone, and no other feature touches these.  A call empties both before it
+ * launches anything, and a refused call leaves them empty.
+ *
+ * SME_EINVAL (the message names the query where there is one): candidates not
+ * strictly ascending, offsets of either kind not ascending from 0, a term id outside
+ * [-1, V), width < 1, m < 0, min_cover < 0, an order or a with_terms other than 0 / 1,
+ * nq < 0.  SME_ELIMIT: width > 256; more than 64 distinct or 1024 listed ids in a
+ * query; 2^31 or more candidates, or listed ids, in a batch; 2^31 or more window term
+ * entries.  nq == 0, a query without candidates and a query without ids are valid.
+ *
+ * sme_query_passages_stats reports on the last passages call: the batch's candidates,
+ * those with at least one record, the stream positions of their records (each counted
+ * once per candidate), the kept rows before the cut, and the window starts a wave of
+ * the scan kernel takes at a time (its chunk length). */
+typedef struct sme_passages {
+  const int64_t *res_off; /* [nq + 1] */
+  const int32_t *docno, *rec, *start, *len, *hits;
+  const uint64_t *mask;
+  const double *score;
+  int64_t total;
+  const int64_t *win_off; /* [total + 1], or the one entry 0 */
+  const int32_t *win_term;
+  const int8_t *win_slot;
+  int64_t win_total;
+} sme_passages;
+int sme_query_passages(sme_index *ix, const int32_t *term_ids, const int64_t *q_offsets, const int32_t *docnos,
+                       const int64_t *d_offsets, int nq, int width, int min_cover, int order, int m, int with_terms,
+                       sme_passages *out);
+int sme_query_passages_device(sme_index *ix, const int32_t *term_ids, const int64_t *q_offsets,
+                              const int32_t *d_docnos, const int64_t *d_doc_offsets, int nq, int width, int min_cover,
+                              int order, int m, int with_terms, void *stream, sme_passages *out);
+int sme_query_passages_stats(const sme_index *ix, uint64_t *candidates, uint64_t *with_record, uint64_t *positions,
+                             uint64_t *kept, uint64_t *chunk);
+
 /* 128-bit fingerprint of every index term (two u64 per term into device memory
  * d_out[2 V]): equal term strings (k-grams) on different shards get equal
  * fingerprints, so a multi-GPU df exchange can key the all-reduce on them

@@ -12,6 +12,7 @@ classes; see include/sme.h for the C-ABI each call goes through):
 Everything computes on the GPU through libsme.so.  There is no CPU fallback:
 if the HIP library is missing or no GPU is visible, calls raise SmeError.
 """
+import collections
 import ctypes as C
 import os
 import struct
@@ -37,6 +38,26 @@ class SmeError(RuntimeError):
 class _Config(C.Structure):
     _fields_ = [("k", C.c_int), ("num_partitions", C.c_int), ("idf_mode", C.c_int), ("tiebreak", C.c_int),
                 ("device", C.c_int), ("reserved", C.c_int * 11)]
+
+
+class _Passages(C.Structure):
+    """sme_passages (include/sme.h): the rows and the window terms of a passages call."""
+    _fields_ = [("res_off", C.c_void_p), ("docno", C.c_void_p), ("rec", C.c_void_p), ("start", C.c_void_p),
+                ("len", C.c_void_p), ("hits", C.c_void_p), ("mask", C.c_void_p), ("score", C.c_void_p),
+                ("total", C.c_int64), ("win_off", C.c_void_p), ("win_term", C.c_void_p), ("win_slot", C.c_void_p),
+                ("win_total", C.c_int64)]
+
+
+_PASSAGE_FIELDS = ("res_off", "docno", "rec", "start", "len", "hits", "mask", "score", "win_off", "win_term",
+                   "win_slot")
+Passages = collections.namedtuple("Passages", _PASSAGE_FIELDS)
+DevicePassages = collections.namedtuple("DevicePassages", _PASSAGE_FIELDS + ("total", "win_total"))
+
+
+def snippet(vocabulary, win_term, win_slot):
+    """A window as text: its term strings in stream order, the hits (slot >= 0) in
+    square brackets.  vocabulary: Index.terms(), or anything indexed by term id."""
+    return " ".join("[%s]" % vocabulary[int(t)] if s >= 0 else vocabulary[int(t)] for t, s in zip(win_term, win_slot))
 
 
 _lib = None
@@ -67,6 +88,7 @@ EXPORTS = [
     "sme_index_prepare_bm25", "sme_index_doc_lengths", "sme_index_bm25_stats", "sme_query_topk_bm25",
     "sme_query_topk_bm25_device", "sme_query_bm25_stats",
     "sme_query_rescore", "sme_query_rescore_device", "sme_query_rescore_stats",
+    "sme_query_passages", "sme_query_passages_device", "sme_query_passages_stats",
 ]
 
 
@@ -205,6 +227,9 @@ def lib():
                                            C.c_int, C.c_int, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
                                            C.POINTER(vp), i64p]
     L.sme_query_rescore_stats.argtypes = [vp] + [C.POINTER(C.c_uint64)] * 4
+    L.sme_query_passages.argtypes = [vp, i32p, i64p, i32p, i64p] + [C.c_int] * 6 + [C.POINTER(_Passages)]
+    L.sme_query_passages_device.argtypes = [vp, i32p, i64p, vp, vp] + [C.c_int] * 6 + [vp, C.POINTER(_Passages)]
+    L.sme_query_passages_stats.argtypes = [vp] + [C.POINTER(C.c_uint64)] * 5
     _lib = L
     return L
 
@@ -583,7 +608,8 @@ class Index:
     # ---- the batched query features: n queries in, n + 1 offsets and one to four
     # value columns out (include/sme.h).  The four patterns below are each written
     # once; a feature names its entry, its input dtypes and its column dtypes.
-    _CT = {np.int32: C.c_int32, np.int64: C.c_int64, np.uint8: C.c_uint8, np.float64: C.c_double}
+    _CT = {np.int32: C.c_int32, np.int64: C.c_int64, np.uint8: C.c_uint8, np.float64: C.c_double, np.int8: C.c_int8,
+           np.uint64: C.c_uint64}
 
     @staticmethod
     def _typed_ptrs(arrays, dtypes):
@@ -1178,6 +1204,67 @@ class Index:
         c, f, mt, t = Index._stats(self._h, lib().sme_query_rescore_stats, 4)
         return {"candidates": c, "found": f, "matches": mt, "tile": t}
 
+    # ---- best passages (include/sme.h, sme_query_passages)
+    _PASSAGE_DTYPES = (np.int64, np.int32, np.int32, np.int32, np.int32, np.int32, np.uint64, np.float64, np.int64,
+                       np.int32, np.int8)
+
+    def passages(self, term_ids, q_offsets, docnos, d_offsets, width, min_cover=0, order=0, m=0, with_terms=False):
+        """sme_query_passages: for query i's term ids term_ids[q_offsets[i]:q_offsets[i+1]]
+        and each of its candidates docnos[d_offsets[i]:d_offsets[i+1]], strictly
+        ascending, the best window of at most `width` (1..256) consecutive positions of
+        one of the document's records: -1 dropped and repeats folded, the j-th distinct
+        id is slot j; a window's mask ORs the slots it holds, hits counts the matching
+        positions, score sums the covered slots' idfs; the best is the first by score,
+        cover, hits descending, then rec, start ascending.  Candidates covering
+        min_cover slots or more are kept, in the given order (order 0) or by score
+        descending then docno ascending (order 1), cut to the first m (0: no cut).
+        Returns Passages(res_off int64[nq+1], docno, rec, start, len, hits int32, mask
+        uint64, score float64, win_off, win_term, win_slot): with_terms, row r's
+        window is win_term / win_slot[win_off[r]:win_off[r+1]], the stream's term ids
+        and each one's slot or -1 (snippet() renders it); else win_off is [0] and both
+        are empty.  The index must keep positions (Index.positions)."""
+        keep, ptrs = Index._typed_ptrs([term_ids, q_offsets, docnos, d_offsets], (np.int32, np.int64, np.int32, np.int64))
+        nq = len(keep[1]) - 1
+        r = _Passages()
+        _check(lib().sme_query_passages(self._h, *ptrs, nq, int(width), int(min_cover), int(order), int(m),
+                                        int(with_terms), C.byref(r)))
+        counts = [nq + 1] + [r.total] * 7 + [r.total + 1 if with_terms else 1] + [r.win_total] * 2
+
+        def arr(name, n, dt):
+            ptr = getattr(r, name)
+            return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(Index._CT[dt])), (n,)).copy() if n else np.zeros(0, dt)
+        return Passages(*[arr(f, n, dt) for f, n, dt in zip(_PASSAGE_FIELDS, counts, Index._PASSAGE_DTYPES)])
+
+    def passages_device(self, term_ids, q_offsets, d_docnos, d_doc_offsets, width, min_cover=0, order=0, m=0,
+                        with_terms=False, stream=None):
+        """sme_query_passages_device: the candidates and their nq + 1 offsets in device
+        memory (pointers, or contiguous int32 / int64 device tensors) -- the docno
+        and res_off pointers of another feature's order 0 device call as they stand;
+        the term ids and their offsets are host arrays.  Returns DevicePassages: the
+        device pointers of Passages' arrays (0 for an empty one), total (the rows)
+        and win_total; they belong to the index until its next passages call."""
+        keep, ptrs = Index._typed_ptrs([term_ids, q_offsets], (np.int32, np.int64))
+        nq = len(keep[1]) - 1
+        dev = [C.c_void_p((x.data_ptr() if hasattr(x, "data_ptr") else x) or 0) for x in (d_docnos, d_doc_offsets)]
+        r = _Passages()
+        _check(lib().sme_query_passages_device(self._h, *ptrs, *dev, nq, int(width), int(min_cover), int(order),
+                                               int(m), int(with_terms), C.c_void_p(stream or 0), C.byref(r)))
+        return DevicePassages(*[getattr(r, f) or 0 for f in _PASSAGE_FIELDS], r.total, r.win_total)
+
+    def passages_stats(self):
+        """The last passages call: {"candidates": the batch's candidates, "with_record":
+        those with at least one record, "positions": the stream positions of their
+        records, "kept": the rows before the cut, "chunk": the window starts a wave of
+        the scan takes at a time}."""
+        c, w, p, k, ch = Index._stats(self._h, lib().sme_query_passages_stats, 5)
+        return {"candidates": c, "with_record": w, "positions": p, "kept": k, "chunk": ch}
+
+    def snippet(self, passages, row, vocabulary=None):
+        """Row `row` of a with_terms Passages result as text, hits bracketed (snippet())."""
+        a, e = int(passages.win_off[row]), int(passages.win_off[row + 1])
+        return snippet(vocabulary if vocabulary is not None else self.terms(), passages.win_term[a:e],
+                       passages.win_slot[a:e])
+
     def reweight(self, n_global, d_df_global=None, stream=None):
         """TF-IDF weights with all-reduced N (and df) of a doc-sharded index."""
         _check(lib().sme_index_reweight(self._h, n_global, C.c_void_p(d_df_global or 0), C.c_void_p(stream or 0)))
@@ -1597,6 +1684,24 @@ class IntDocVectorsForwardIndex:
             return [int(d) for d in dn]
         self._scorer(scorer)
         return self._rescored(self.index.query_near_device([near], order=0, m=0), near[0], scorer, k, k1, b)
+
+    def get_passages(self, query, docnos, width=32):
+        """Where the query matched in the given documents: the text goes through
+        processContent and the term lookup (unknown tokens skipped), the docnos are
+        sorted and repeats dropped, and every document's best window of at most
+        `width` positions comes back (Index.passages, every candidate kept, in docno
+        order) as a list of dicts: docno, rec, start, len, hits, cover (the distinct
+        query terms in the window), score and snippet, the window's terms with the
+        hits in square brackets.  A docno without a record has rec -1 and an empty
+        snippet.  The index must keep positions (Index.positions)."""
+        ids = [int(t) for t in self.index.lookup(self.index.ctx.process_content(query)) if t >= 0]
+        cands = sorted(set(int(d) for d in docnos))
+        r = self.index.passages(ids, [0, len(ids)], cands, [0, len(cands)], width, with_terms=True)
+        if getattr(self, "_vocabulary", None) is None:
+            self._vocabulary = self.index.terms()
+        return [{"docno": int(r.docno[i]), "rec": int(r.rec[i]), "start": int(r.start[i]), "len": int(r.len[i]),
+                 "hits": int(r.hits[i]), "cover": bin(int(r.mask[i])).count("1"), "score": float(r.score[i]),
+                 "snippet": self.index.snippet(r, i, self._vocabulary)} for i in range(len(r.docno))]
 
     def get_similar(self, docno, terms=25):
         """More like this: the `terms` best feedback terms of the one document

@@ -12,6 +12,7 @@
 #include <thread>
 
 #include "sme_bm25.hpp"
+#include "sme_passage.hpp"
 #include "sme_rescore.hpp"
 #include "sme_feedback.hpp"
 #include "sme_internal.hpp"
@@ -1472,6 +1473,118 @@ int sme_query_rescore_stats(const sme_index *ix, uint64_t *candidates, uint64_t 
     if (!ix || !candidates || !found || !matches || !tile) throw sme::Error(SME_EINVAL, "null argument");
     pass_stats(ix->rs, candidates, found, matches);
     *tile = (uint64_t)sme::rescore::kTile;
+  });
+}
+
+// Best passages read the term streams of a K = 1 index and the idfs of its query
+// side.  A call empties both of its results first, so whatever refuses it -- here or
+// in sme::query_passages, which validates the batch -- leaves them empty.
+static void need_passages_index(sme_index *ix) {
+  if (!ix) throw sme::Error(SME_EINVAL, "null index");
+  ix->pw.reset();
+  ix->pwt.reset();
+  ix->pw_with_record = ix->pw_positions = 0;
+  if (ix->job != 0) throw sme::Error(SME_EINVAL, "passages: a CharKGramTermIndexer output has no term streams");
+  if (ix->records_only)
+    throw sme::Error(SME_EINVAL, "passages: records-only index (merged shard pieces) has no query side");
+  if (ix->K != 1) throw sme::Error(SME_EINVAL, "passages: the index holds k-grams (K != 1), not terms");
+  if (!ix->has_positions)
+    throw sme::Error(SME_EINVAL, "passages: the index keeps no positions (build it with option \"positions\" 1)");
+}
+static void need_passages_args(const int32_t *term_ids, const int64_t *q_offsets, const int32_t *docnos,
+                               const int64_t *d_offsets, int nq, int min_cover, int order, int m, int with_terms) {
+  if (nq < 0) throw sme::Error(SME_EINVAL, "passages: nq must be >= 0");
+  if (nq > 0 && (!q_offsets || !d_offsets)) throw sme::Error(SME_EINVAL, "null argument");
+  if (order != 0 && order != 1) throw sme::Error(SME_EINVAL, "passages: order must be 0 (as given) or 1 (score)");
+  if (with_terms != 0 && with_terms != 1) throw sme::Error(SME_EINVAL, "passages: with_terms must be 0 or 1");
+  if (m < 0) throw sme::Error(SME_EINVAL, "passages: m must be >= 0");
+  if (min_cover < 0) throw sme::Error(SME_EINVAL, "passages: min_cover must be >= 0");
+  // (offsets that do not start at 0 are refused by the validator before these arrays are read)
+  if (nq > 0 && q_offsets[0] == 0 && q_offsets[nq] > 0 && !term_ids) throw sme::Error(SME_EINVAL, "null argument");
+  if (nq > 0 && d_offsets[0] == 0 && d_offsets[nq] > 0 && !docnos) throw sme::Error(SME_EINVAL, "null argument");
+}
+static void passages_device_arrays(const sme_index *ix, sme_passages *out) {
+  const sme::PassageRows &r = ix->pw;
+  const sme::WindowTerms &w = ix->pwt;
+  *out = sme_passages{r.dev_offsets(),
+                      r.dev<sme::PassageRows::docno>(),
+                      r.dev<sme::PassageRows::rec>(),
+                      r.dev<sme::PassageRows::start>(),
+                      r.dev<sme::PassageRows::len>(),
+                      r.dev<sme::PassageRows::hits>(),
+                      r.dev<sme::PassageRows::mask>(),
+                      r.dev<sme::PassageRows::score>(),
+                      r.total,
+                      w.dev_offsets(),
+                      w.dev<sme::WindowTerms::term>(),
+                      w.dev<sme::WindowTerms::slot>(),
+                      w.total};
+}
+
+int sme_query_passages_device(sme_index *ix, const int32_t *term_ids, const int64_t *q_offsets,
+                              const int32_t *d_docnos, const int64_t *d_doc_offsets, int nq, int width, int min_cover,
+                              int order, int m, int with_terms, void *stream, sme_passages *out) {
+  return guard([&] {
+    if (!out) throw sme::Error(SME_EINVAL, "null argument");
+    need_passages_index(ix);  // (before anything is copied for it)
+    if (nq > 0 && !d_doc_offsets) throw sme::Error(SME_EINVAL, "null argument");
+    set_device(ix->ctx);
+    hipStream_t st = stream_of(ix->ctx, stream);
+    // the candidates' offsets come to the host, where they are validated
+    std::vector<int64_t> offs((size_t)std::max(nq, 0) + 1, 0);
+    if (nq > 0) {
+      SME_HIP(hipMemcpyAsync(offs.data(), d_doc_offsets, offs.size() * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+      SME_HIP(hipStreamSynchronize(st));
+    }
+    // (a device array of candidates is not read here: any non-null value stands for it)
+    need_passages_args(term_ids, q_offsets, d_docnos, offs.data(), nq, min_cover, order, m, with_terms);
+    sme::query_passages(ix, term_ids, q_offsets, d_docnos, true, offs.data(), d_doc_offsets, nq, width, min_cover, order,
+                        m, with_terms, st);
+    passages_device_arrays(ix, out);
+  });
+}
+
+int sme_query_passages(sme_index *ix, const int32_t *term_ids, const int64_t *q_offsets, const int32_t *docnos,
+                       const int64_t *d_offsets, int nq, int width, int min_cover, int order, int m, int with_terms,
+                       sme_passages *out) {
+  return guard([&] {
+    if (!out) throw sme::Error(SME_EINVAL, "null argument");
+    need_passages_index(ix);
+    need_passages_args(term_ids, q_offsets, docnos, d_offsets, nq, min_cover, order, m, with_terms);
+    set_device(ix->ctx);
+    hipStream_t st = ix->ctx->own_stream;
+    sme::query_passages(ix, term_ids, q_offsets, docnos, false, d_offsets, nullptr, nq, width, min_cover, order, m,
+                        with_terms, st);
+    sme::PassageRows &r = ix->pw;
+    sme::WindowTerms &w = ix->pwt;
+    r.fetch(st);
+    w.fetch(st);
+    *out = sme_passages{r.h_off.data(),
+                        r.host<sme::PassageRows::docno>(),
+                        r.host<sme::PassageRows::rec>(),
+                        r.host<sme::PassageRows::start>(),
+                        r.host<sme::PassageRows::len>(),
+                        r.host<sme::PassageRows::hits>(),
+                        r.host<sme::PassageRows::mask>(),
+                        r.host<sme::PassageRows::score>(),
+                        r.total,
+                        w.h_off.data(),
+                        w.host<sme::WindowTerms::term>(),
+                        w.host<sme::WindowTerms::slot>(),
+                        w.total};
+  });
+}
+
+int sme_query_passages_stats(const sme_index *ix, uint64_t *candidates, uint64_t *with_record, uint64_t *positions,
+                             uint64_t *kept, uint64_t *chunk) {
+  return guard([&] {
+    if (!ix || !candidates || !with_record || !positions || !kept || !chunk)
+      throw sme::Error(SME_EINVAL, "null argument");
+    *candidates = ix->pw.cands;
+    *with_record = ix->pw_with_record;
+    *positions = ix->pw_positions;
+    *kept = ix->pw.matches;
+    *chunk = (uint64_t)sme::passage::kChunk;
   });
 }
 

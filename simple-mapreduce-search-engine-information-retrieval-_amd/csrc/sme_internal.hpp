@@ -244,6 +244,12 @@ struct sme_index {
   // slots whose list holds the document; cands: the batch's candidates, verified:
   // the sum of those hits)
   sme::DocFreqScores rs;
+  // best passages (sme_passage.hip): the last call's rows (cands: the batch's
+  // candidates, matches: the rows before the cut) and, if it asked for them, the
+  // rows' window terms; the candidates with a record and their stream positions
+  sme::PassageRows pw;
+  sme::WindowTerms pwt;
+  uint64_t pw_with_record = 0, pw_positions = 0;
   // stage timings of the build that produced this index (ms)
   std::vector<std::pair<std::string, float>> profile;
   ~sme_index() { ctx->live_indexes--; }  // members (pooled buffers) are released after this body
@@ -255,7 +261,8 @@ struct sme_index {
                            &d_ps_docno, &d_nq_lut, &d_pf_file, &d_bm_dl, &d_bm_idf, &d_bm_maxtf, &d_bm_mindl, &d_bm_norm,
                            &d_bm_stat})
       b->pool = &c->pool;
-    for (sme::ResultSet *r : std::initializer_list<sme::ResultSet *>{&wx, &fz, &bq, &pq, &nq, &sq, &sv, &fb, &rs})
+    for (sme::ResultSet *r : std::initializer_list<sme::ResultSet *>{&wx, &fz, &bq, &pq, &nq, &sq, &sv, &fb, &rs, &pw,
+                                                                     &pwt})
       r->bind(&c->pool);
   }
 };
@@ -551,6 +558,15 @@ void query_topk_bm25(sme_index *ix, const int32_t *d_terms, const int64_t *d_qof
 void rescore_docs(sme_index *ix, const int32_t *term_ids, const int64_t *q_offsets, const int32_t *docnos,
                   bool on_device, const int64_t *d_offsets, const int64_t *d_offsets_dev, int nq, int model, double k1,
                   double b, int min_hits, int order, int m, hipStream_t st);
+// best passages (sme_passage.hip): nq queries of term ids and strictly ascending
+// candidate docnos, given as rescore_docs takes them -> per candidate the best window
+// of at most `width` positions of one of its records' streams; the candidates whose
+// window covers min_cover distinct query terms or more kept, ordered (0 as given, 1
+// score desc then docno asc) and cut to m: ix->pw; with_terms: the kept windows'
+// term ids and slots: ix->pwt
+void query_passages(sme_index *ix, const int32_t *term_ids, const int64_t *q_offsets, const int32_t *docnos,
+                    bool on_device, const int64_t *d_offsets, const int64_t *d_offsets_dev, int nq, int width,
+                    int min_cover, int order, int m, int with_terms, hipStream_t st);
 // The idf of a term with document frequency df among N documents, the one
 // expression behind the build's idf tables (idf_by_df[df] = idf_value(N, df),
 // idf_by_q[q] = idf_value(q, 1) read at q = N / df: log10 of the integer quotient)

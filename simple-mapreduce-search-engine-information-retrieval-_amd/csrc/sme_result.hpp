@@ -1,5 +1,5 @@
 // sme_result.hpp -- what a batched query call leaves on the index: n + 1 offsets
-// and up to four value columns of `total` entries, query i's values at
+// and up to seven value columns of `total` entries, query i's values at
 // [off[i], off[i + 1]), beside the call's counts.
 //
 // Ownership: the device arrays and the host mirrors belong to the index until the
@@ -21,7 +21,7 @@
 namespace sme {
 
 struct ResultSet {
-  static constexpr int kMaxCols = 4;
+  static constexpr int kMaxCols = 7;
   struct Column {
     DevBuf d;                // [total] elements of esize bytes
     size_t esize = 0;        // 0: no such column
@@ -99,6 +99,14 @@ struct DocFreqScores : ResultOf<int32_t, int32_t, double> {  // phrase / proximi
 };
 struct TermFreqDocsScores : ResultOf<int32_t, int32_t, int32_t, double> {  // relevance feedback (sme_feedback.hip)
   enum { term, freq, docs, score };  // a set's terms; their occurrences; the set's documents holding them; their scores
+};
+struct PassageRows : ResultOf<int32_t, int32_t, int32_t, int32_t, int32_t, uint64_t, double> {  // best passages (sme_passage.hip)
+  // a kept candidate; its best window's record ordinal, first position and length; the
+  // window's hits; the slots it covers; the sum of their idfs
+  enum { docno, rec, start, len, hits, mask, score };
+};
+struct WindowTerms : ResultOf<int32_t, int8_t> {  // best passages: the rows' windows, row i's at offsets i, i + 1
+  enum { term, slot };  // the stream's term ids; each one's slot in its row's query, or -1
 };
 
 }  // namespace sme
